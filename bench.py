@@ -24,8 +24,14 @@ and relays rank 0's line; under an external torchrun ``--gpus`` must equal WORLD
 RCCL; the timed region is bracketed by barriers and the time is the max over ranks.  ``--dry-run`` exercises the
 launcher and the distributed timing on CPU (gloo), with no GPU.
 
-The default run (N=1, config 2, train_fwd) also times, in the same process and as extra keys of its one line, the
-training step (``train_step``: config 2 with backward + Adam), the reference's own shell setting of it
+A plain run (no ``--full``) does what the headline figure needs and no more: set up, ``--warmup`` untimed and
+``--steps`` timed steps, the outputs of the last timed step when ``--dump-outputs DIR`` asks for them, the line.  Its
+roofline comes from the HIP events of the last timed step; ``cpu_baseline`` and ``cd_vs_ref`` are null, and no detail
+file is written unless ``--detail`` names one.  The CPU baseline and CD vs the oracle, the fp32-MFMA comparison, the
+extra lines and the measured ceiling belong to ``--full``.
+
+With ``--full`` the default run (N=1, config 2, train_fwd) also times, in the same process and as extra keys of its
+one line, the training step (``train_step``: config 2 with backward + Adam), the reference's own shell setting of it
 (``train_step_refcfg``: 256 rays at 768 + 1536 samples, chunk 262,144, shells/pretraining/KITTI00_pcnerf_train.bash),
 BASELINE configs 3 (``config3``) and 4 (``config4``, all four MaiCity blocks on the one GPU), ``val`` and the
 two-step ``view``, each with its own ms_per_step, roofline, cpu_baseline and cd_vs_ref (--no-extra
@@ -80,6 +86,16 @@ def parse(argv=None):
     ap.add_argument("--cpu-rays", type=int, default=None,
                     help="bounded CPU-baseline sample (rays; default %d on every line, or the whole line when "
                          "smaller; ray groups for view)" % CPU_SAMPLE_RAYS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baseline and CD vs the oracle, the fp32-MFMA "
+                         "comparison run, the extra lines of the default run, the measured fp16 MFMA ceiling and the "
+                         "default --detail file (each still has its own --no-... switch).  Without it a run sets up, "
+                         "warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (the render's result arrays "
+                         "and the loss of rank 0's blocks) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed "
+                         "seeded row sample of a larger array) and DIR/manifest.json; the same arguments give the "
+                         "same inputs and draws in every run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp32-line", action="store_true",
                     help="skip the comparison run of the train lines under the fp32 MFMA train math (profiling)")
@@ -99,6 +115,10 @@ def parse(argv=None):
                     help="file for every line in full (kernel tables, fp32-MFMA comparison); '' for none. stdout "
                          "carries only the compact line (<= 4 KB)")
     a = ap.parse_args(argv)
+    if not a.full:   # the plain run: the headline's own steps and nothing beside them
+        a.no_cpu_baseline = a.no_fp32_line = a.no_extra = a.no_ceiling = True
+        if a.detail == ap.get_default("detail"):   # the detail file only where the caller names one
+            a.detail = ""
     a.mode = a.mode or MODE_OF_CONFIG[a.config]
     if a.samples is None:
         a.samples = 64 if a.config == 3 else 128
@@ -391,7 +411,8 @@ def main(argv=None):
     extras = {}
     if world == 1 and a.config == 2 and a.mode == "train_fwd" and not a.fold and not a.no_extra:
         for name, over in EXTRA_LINES.items():
-            b = argparse.Namespace(**{**vars(a), **over, "no_fp32_line": True, "gather": False})
+            b = argparse.Namespace(**{**vars(a), **over, "no_fp32_line": True, "gather": False,
+                                      "dump_outputs": None})
             extras[name] = run_line(b, L, dev, rank, world)
     if rank != 0:
         if dist:
@@ -521,6 +542,8 @@ def run_line(a, L, dev, rank, world):
     view = a.mode == "view"
     train = a.mode in ("train_fwd", "train_step")
     grad = a.mode == "train_step"
+    # the render's perturb / resample draws come from torch's generator: the same arguments, the same draws
+    torch.manual_seed(1234 + rank)
     if a.fold:
         if train:
             _ops.set_train_fold(True)
@@ -562,6 +585,8 @@ def run_line(a, L, dev, rank, world):
             res = render_rays_val(mc, mf, emb, rays, N_samples=a.samples, N_importance=a.importance, perturb=0,
                                   noise_std=0, chunk=a.chunk)
             loss = 1e-1 * loss_fn(1e1 * res["depth_fine"], 1e1 * gt)
+        if dump["on"]:   # --dump-outputs, last timed step: what the caller of the path received (references only)
+            dump["res"][blk["block"]] = dict(res, loss=loss)
         return loss, res["depth_fine"]
 
     def step():
@@ -591,6 +616,8 @@ def run_line(a, L, dev, rank, world):
 
     breakdown = {}   # wall time of the instrumented (last) step, the one the kernel breakdown comes from
     coll = {"on": False, "events": []}   # collective events of the timed steps (N > 1)
+    # --dump-outputs (rank 0): every block's result of the headline's last timed step
+    dump = {"want": bool(a.dump_outputs) and rank == 0, "on": False, "res": {}}
 
     def timed(steps, warmup):
         """warmup, barrier, ``steps`` timed steps (HIP events on the last), barrier; max over ranks."""
@@ -611,7 +638,9 @@ def run_line(a, L, dev, rank, world):
                     L.pcnerf_prof_enable(1)
                     eb0 = torch.cuda.Event(enable_timing=True)
                     eb0.record()
+                    dump["on"] = dump["want"]
                 loss = step()
+            dump["on"] = False
             if eb0 is not None:
                 eb1 = torch.cuda.Event(enable_timing=True)
                 eb1.record()
@@ -633,6 +662,10 @@ def run_line(a, L, dev, rank, world):
     eval_math = None if (train or a.fold) else _ops.get_eval_math()
     log(f"{a.mode} ({a.rays} rays, {a.samples}/{a.importance}): {a.warmup} + {a.steps} steps")
     elapsed, loss_val = timed(a.steps, a.warmup)
+    if dump["want"]:
+        dump_outputs(a.dump_outputs, dump["res"])
+        dump["want"] = False
+        dump["res"].clear()
     dist_info = None
     if dist:   # the self-proving N-rank record: who ran, over which backend, each rank's work and time
         n_loc = (sum(blk.get("groups", a.rays) for blk in blocks) if view
@@ -710,6 +743,37 @@ def run_line(a, L, dev, rank, world):
                          "remat: no activation store, no memory budget set -- the drop-in's default training path "
                          "(nof._ops.set_train_backward)" if _ops.remat_enabled() else
                          "store: activation store, budget free HBM - 4 GiB (opt-in)")}
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: every .npy file together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: ``results`` {block: {name: tensor}} (the render's result dict and the loss of the last timed
+    step) as ``path/<name>.npy`` (``block<b>_<name>`` when there are several blocks), float32 (integers float64).
+    Every array gets an equal share of DUMP_MAX_BYTES; a larger one keeps a fixed sample of its rows (sorted row
+    numbers from numpy's default_rng(DUMP_SAMPLE_SEED)), recorded with the full shapes in ``path/manifest.json``."""
+    os.makedirs(path, exist_ok=True)
+    named = {(k if len(results) == 1 else f"block{b}_{k}"): v
+             for b, res in sorted(results.items()) for k, v in res.items() if torch.is_tensor(v)}
+    cap = DUMP_MAX_BYTES // max(len(named), 1)
+    manifest = {}
+    for name, v in named.items():
+        v = v.detach()
+        arr = v.to(torch.float32 if v.is_floating_point() or v.dtype == torch.bool else torch.float64).cpu().numpy()
+        info ={"shape": list(arr.shape), "dtype": str(arr.dtype), "rows_kept": None}
+        if arr.nbytes > cap:
+            rows = arr.shape[0]
+            n = max(1, cap // (arr.nbytes // rows))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, n, replace=False))
+            arr = arr[idx]
+            info.update(rows_kept=int(n), sample_seed=DUMP_SAMPLE_SEED)
+        np.save(os.path.join(path, name + ".npy"), arr)
+        manifest[name] = info
+    with open(os.path.join(path, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
+    log(f"outputs of the last timed step: {len(manifest)} arrays in {path}")
 
 
 def rank_report(tdist, dev, n_local, local_s, coll_ms, steps):

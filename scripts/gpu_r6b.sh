@@ -14,6 +14,7 @@ for v in 1 0 1 0; do   # layer 1's launch with dW_0's encoding columns fused (1,
   PCNERF_REMAT_FUSE0=$v timeout -k 10 300 python3 bench.py --mode train_step --steps 10 --warmup 3 --no-extra --no-ceiling --no-cpu-baseline --no-fp32-line --detail gpurun_out/r6b_ts_f$v.detail.json > gpurun_out/r6b_ts_f$v.json 2> gpurun_out/r6b_ts_f$v.err
   rc=$?; echo "train_step fuse0=$v rc=$rc $(cut -c1-200 gpurun_out/r6b_ts_f$v.json)"; [ $rc -ne 0 ] && exit $rc
 done
-timeout -k 10 400 python3 bench.py --config 5 --steps 5 --warmup 2 --no-ceiling --detail gpurun_out/r6b_c5.detail.json > gpurun_out/r6b_c5.json 2> gpurun_out/r6b_c5.err
+C5=${PCNERF_PARITY_REPORT%_report.jsonl}_c5   # beside the parity report
+timeout -k 10 400 python3 bench.py --full --config 5 --steps 5 --warmup 2 --no-ceiling --detail $C5.detail.json > $C5.json 2> $C5.err
 rc=$?; echo "config5 rc=$rc $(cut -c1-300 gpurun_out/r6b_c5.json)"
 exit $rc

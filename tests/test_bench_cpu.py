@@ -122,6 +122,49 @@ def test_cpu_baseline_sample_is_fixed(bench):
     assert n == 3 and out == 3
 
 
+def test_plain_run_does_only_the_headline(bench):
+    """Without --full a run times its steps and nothing beside them (no CPU baseline, fp32 comparison, extra lines,
+    ceiling, default detail file); --full leaves every switch to the caller, as before."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup) == (7, 3) and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_fp32_line and a.no_extra and a.no_ceiling and a.detail == ""
+    assert bench.parse(["--detail", "d.json"]).detail == "d.json"
+    f = bench.parse(["--full"])
+    assert not (f.no_cpu_baseline or f.no_fp32_line or f.no_extra or f.no_ceiling) and f.detail
+    assert bench.parse(["--full", "--no-extra"]).no_extra
+
+
+def test_dump_outputs_files_and_budget(bench, tmp_path):
+    """--dump-outputs: one float32 / float64 .npy per result array, small arrays whole, a larger one as the same
+    sorted row sample in every run, and never more than DUMP_MAX_BYTES in all."""
+    import json
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    big = torch.rand(70000, 384, generator=g)   # 107.5 MB: over its share
+    res = {0: {"depth_fine": torch.rand(1000, generator=g), "weights": big, "flag": torch.rand(1000, generator=g) > 0.5,
+               "loss": torch.tensor(0.25, requires_grad=True) * 2, "count": torch.arange(5)}}
+    out = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res)
+        out.append({p.stem: np.load(p) for p in sorted((tmp_path / d).glob("*.npy"))})
+    assert set(out[0]) == {"depth_fine", "weights", "flag", "loss", "count"}
+    assert sum(v.nbytes for v in out[0].values()) <= bench.DUMP_MAX_BYTES
+    for k, v in out[0].items():
+        assert v.dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(v, out[1][k])
+    np.testing.assert_array_equal(out[0]["depth_fine"], res[0]["depth_fine"].numpy())
+    assert out[0]["loss"] == 0.5 and out[0]["count"].dtype == np.float64
+    m = json.loads((tmp_path / "a" / "manifest.json").read_text())
+    n = m["weights"]["rows_kept"]
+    assert m["weights"]["shape"] == [70000, 384] and out[0]["weights"].shape == (n, 384) and n > 1000
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(70000, n, replace=False))
+    np.testing.assert_array_equal(out[0]["weights"], big.numpy()[idx])
+    two = {0: {"depth": torch.zeros(4)}, 3: {"depth": torch.ones(4)}}
+    bench.dump_outputs(str(tmp_path / "c"), two)
+    assert sorted(p.name for p in (tmp_path / "c").glob("*.npy")) == ["block0_depth.npy", "block3_depth.npy"]
+
+
 def test_dist_on_only_for_n_ranks_or_the_test_switch(bench, monkeypatch):
     """The N-rank path runs for world > 1, and at world 1 only under the test-only PCNERF_BENCH_FORCE_DIST=1 (the
     one-rank RCCL test); the driver's default N = 1 run never initialises a process group."""

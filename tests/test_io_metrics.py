@@ -16,7 +16,7 @@ from nof import io as nio
 from nof.networks import NOF_coarse, NOF_fine
 from nof import synthetic as syn
 
-REF = "/root/reference"
+IO_FILES = os.path.join(GOLDEN_DIR, "io_files")
 
 # SURVEY.md section 6 (perf/quality baselines): AvgErr m, Acc %, CD m, F
 RECORDED = {"kitti/version_1/two_step": (0.488, 66.65, 0.2239, 0.891),
@@ -45,15 +45,17 @@ def test_metrics_oracle_on_fixture_frame():
     np.testing.assert_allclose(got, g["expected"], rtol=1e-12)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
 def test_read_pcd_reference_files():
+    """Files as the reference wrote them (tests/golden/io_files, make_io_files.py: the first 4,096 points of each
+    cloud under its own header, the pose file whole) against the clouds the independent reader took from the whole
+    files (metrics_frame)."""
     g = golden("metrics_frame")
-    base = os.path.join(REF, "logs/kitti00/1151_1200_view/render_result")
-    np.testing.assert_array_equal(nio.read_pcd(f"{base}/source/1153_source.pcd"), g["gt"])
-    np.testing.assert_array_equal(nio.read_pcd(f"{base}/infer/version_1_1153_two_step.pcd"), g["pred"])
-    np.testing.assert_array_equal(nio.read_pcd(f"{base}/source/1153_pose.pcd").reshape(-1), g["origin"])
-    pts = nio.read_pcd(os.path.join(REF, "data/kitti/00/pcd_remove_dynamic/1151.pcd"))
+    np.testing.assert_array_equal(nio.read_pcd(f"{IO_FILES}/1153_source.pcd"), g["gt"][:4096])
+    np.testing.assert_array_equal(nio.read_pcd(f"{IO_FILES}/version_1_1153_two_step.pcd"), g["pred"][:4096])
+    np.testing.assert_array_equal(nio.read_pcd(f"{IO_FILES}/1153_pose.pcd").reshape(-1), g["origin"])
+    pts = nio.read_pcd(f"{IO_FILES}/1151.pcd")
     assert pts.ndim == 2 and pts.shape[1] == 3 and pts.shape[0] > 1000 and np.isfinite(pts).all()
+    np.testing.assert_array_equal(pts[::16][:100], golden("kitti_frames_full")["f1151"][:100])
 
 
 def test_pcd_roundtrip_binary_and_ascii(tmp_path):
@@ -83,10 +85,12 @@ def test_ray_cache_roundtrip(tmp_path):
     assert rw.shape == (5, 13) and other.tolist() == [1, 0, 2, 0, 0] and tin.tolist() == [1, 0, 1, 1, 0]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data not present")
 def test_reference_two_step_side_files_load():
-    d = os.path.join(REF, "logs/kitti00/1151_1200_view/two_step/1153pcd/childnerf_ray_intersect")
-    other = np.load(os.path.join(d, "other_interest_sub_nerf_number_child.npy"), allow_pickle=False).reshape(-1)
+    """The first whole ray groups (at most 4,096 rows) of the reference's side file of frame 1153, as np.save wrote
+    them (tests/golden/io_files, make_io_files.py)."""
+    other = np.load(os.path.join(IO_FILES, "other_interest_sub_nerf_number_child.npy"),
+                    allow_pickle=False).reshape(-1)
+    assert other.dtype == np.int64 and 4000 < len(other) <= 4096 and other.max() > 0
     # group structure of the committed rows: first row of a group holds k-1, the rest 0 (a2)
     i, n = 0, len(other)
     while i < n:
