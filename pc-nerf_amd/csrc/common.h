@@ -93,6 +93,10 @@ __device__ __forceinline__ float smooth_l1(float a, float b) {
   return d < 1.0f ? 0.5f * d * d : d - 0.5f;
 }
 
+// log rounded once to float32 (logf may be 1 ulp off, and off the same way over a range of arguments: the opacity
+// sums of k_composite and k_view_rows add thousands of logs of nearly equal arguments).
+__device__ __forceinline__ float log32(float x) { return (float)log((double)x); }
+
 
 // ---- float64 64 x 64 tiles on v_mfma_f64_16x16x4_f64 (A[l&15][k=l>>4], B[k=l>>4][l&15], D[(l>>4)+4r][l&15]).
 // Four waves per workgroup, wave w owns the 32 x 32 quadrant (rows 32(w>>1), columns 32(w&1)) as 2 x 2 blocks.

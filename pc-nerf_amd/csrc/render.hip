@@ -497,10 +497,15 @@ __global__ __launch_bounds__(256) void k_composite(const float* __restrict__ P, 
   }
   if (lane == 0) depth[ray] = d;
   if (opac_row) {  // render.py:224: log(0.1 + p) + log(0.1 + (1 - p)) + 2.20727, summed per ray
+    // each log correctly rounded (pcn::log32), as in k_view_rows: over a long faint row logf's error adds up to
+    // several times float32's own distance from the exact sum.  A rolled loop over the row in memory: unrolled
+    // over pv[], the float64 logs would add to the long-row forms' spills
     double op = 0.0;
-#pragma unroll
-    for (int j = 0; j < MAXB; ++j)
-      if (j < nb) op += (double)((logf(0.1f + pv[j]) + logf(0.1f + (1.0f - pv[j]))) + 2.20727f);
+#pragma nounroll
+    for (int j = 0; j < nb; ++j) {
+      const float pj = pr[j];
+      op += (double)((pcn::log32(0.1f + pj) + pcn::log32(0.1f + (1.0f - pj))) + 2.20727f);
+    }
     op = Gp::sum(op, gsh);
     if (lane == 0) opac_row[ray] = op;
   }

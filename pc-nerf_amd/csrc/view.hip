@@ -57,11 +57,18 @@ __global__ __launch_bounds__(256) void k_view_rows(const float* __restrict__ P, 
       zv[j] = zr[j];
       const float fr = 1.0f - pv[j];
       loc *= (double)fr;
-      // opacity term (render.py:354): log(0.1 + p) + log(0.1 + (1 - p)) + 2.20727
-      op += (double)((logf(0.1f + pv[j]) + logf(0.1f + fr)) + 2.20727f);
     } else {
       pv[j] = zv[j] = 0.0f;
     }
+  }
+  // opacity terms (render.py:354): log(0.1 + p) + log(0.1 + (1 - p)) + 2.20727.  Each log is the correctly rounded
+  // float32 one (log in float64, rounded once): the terms cancel to ~2e-6 at p = 0, and logf's error, up to 1 ulp
+  // of 2.3 and of one sign near 0.1, added up over a long faint row to 5 x float32's own distance from the exact
+  // row sum.  A rolled loop over the row in memory: unrolled over pv[], the float64 logs spill the long-row forms
+#pragma nounroll
+  for (int j = 0; j < nb; ++j) {
+    const float pj = pr[j];
+    op += (double)((pcn::log32(0.1f + pj) + pcn::log32(0.1f + (1.0f - pj))) + 2.20727f);
   }
   double T = view_excl_prod(loc, lane);
   double sw = 0.0;
