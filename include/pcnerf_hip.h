@@ -371,6 +371,40 @@ int pcnerf_count_view_rows(const double* points, int64_t n_points, const double*
 int pcnerf_emit_view_rows(const double* points, int64_t n_points, const double* origin, const double* bounds6,
                           int64_t n_children, const double* parent6, int method, int rule, void* workspace,
                           float* rows, float* ranges, int64_t* other, uint8_t* true_in, void* stream);
+/* Uniform-grid child index (the hierarchical parent/child ray-AABB lookup): the child centres binned into cubic
+ * cells, CSR layout, so the two row builders above test the children near a point or a ray instead of all of them.
+ * The *_grid builders write bit for bit what the flat ones write.
+ * pcnerf_build_child_grid: `grid` is a device buffer of pcnerf_child_grid_bytes(n_children) =
+ *   256 + align256((2^22 + 1) * 4) + 2 * align256(n_children * 4) bytes (header, cell_start at the cell cap,
+ *   cell_items and the sort's scratch).  Origin = the centres' minimum, floor((max - min) / cell) + 1 cells per
+ *   axis; `cell` doubles until the grid has at most 2^22 cells (the header keeps the edge in use).  Items are
+ *   ascending inside each cell, so the build is deterministic.  Non-finite centres and cell <= 0 are errors.  The
+ *   call waits for `stream` once (the dimensions are decided on the host).  Bin the centres the query measures
+ *   from: `centers` for train rows, the box midpoints (bounds6[c][a] + bounds6[c][3 + a]) / 2 for two-step rows.
+ * pcnerf_build_train_rays_grid: the 10 nearest centres by expanding rings of cells around the point's cell, exact
+ *   (ties by index as the flat scan); workspace of pcnerf_rays_grid_workspace_bytes(n_points).
+ * pcnerf_count_view_rows_grid / pcnerf_emit_view_rows_grid: the candidates come from a walk of the ray's whole
+ *   line through the grid (a superset of the 0.65 m filter, which is then applied unchanged); the count pass keeps
+ *   per ray its expansion round and the child indices of its <= 64 hits, the emit pass redoes those face tests:
+ *   pcnerf_rays_grid_workspace_bytes(n_points) = pcnerf_rays_workspace_bytes(n_points) +
+ *   align256(n_points * (8 + 64 * 4)) bytes.
+ * Each query reads the grid's header back first (it waits for `stream`) and refuses a grid built over another
+ * number of children. */
+size_t pcnerf_child_grid_bytes(int64_t n_children);
+int pcnerf_build_child_grid(const double* centers, int64_t n_children, double cell, void* grid, size_t grid_bytes,
+                            void* stream);
+size_t pcnerf_rays_grid_workspace_bytes(int64_t n_points);
+int pcnerf_build_train_rays_grid(const double* points, int64_t n_points, const double* origin,
+                                 const double* centers, const double* bounds6, int64_t n_children,
+                                 const double* parent6, double surface_expand, int face_rule, const void* grid,
+                                 void* workspace, float* rows, int64_t* n_rows, int* n_short, void* stream);
+int pcnerf_count_view_rows_grid(const double* points, int64_t n_points, const double* origin,
+                                const double* bounds6, int64_t n_children, const double* parent6, int method,
+                                int rule, const void* grid, void* workspace, int64_t* n_rows, void* stream);
+int pcnerf_emit_view_rows_grid(const double* points, int64_t n_points, const double* origin, const double* bounds6,
+                               int64_t n_children, const double* parent6, int method, int rule, const void* grid,
+                               void* workspace, float* rows, float* ranges, int64_t* other, uint8_t* true_in,
+                               void* stream);
 
 /* ---------------------------------------------------------------- evaluation metrics
  * (nof/criteria/pointcloud_metrics.py:5-49, logs/.../render_result/print_metrics.py:31-133; exhaustive float64

@@ -40,7 +40,7 @@ from nof import dataset as D  # noqa: E402
 from nof.blocks import gather_rows, split_groups  # noqa: E402
 from nof import io as nio  # noqa: E402
 from nof.networks import Embedding, NOF_coarse, NOF_fine  # noqa: E402
-from nof.raytable import build_view_rows  # noqa: E402
+from nof.raytable import ChildGrid, build_view_rows  # noqa: E402
 from nof.render import render_rays_view_0525_2_2  # noqa: E402
 
 
@@ -142,8 +142,9 @@ class Scene:
     (multi_frame_maicity, :246-535): absolute poses (pose j for file j+1), the parent box from the command line,
     child boxes grown by 0.025 (:277-291), scans cut to the parent box."""
 
-    def __init__(self, h, device):
+    def __init__(self, h, device, *, ray_index=D.DEFAULT_RAY_INDEX):
         self.h, self.device = h, torch.device(device)
+        self.ray_index, self._grid = ray_index, None   # "grid": one ChildGrid over the child boxes, every frame
         self.maicity = h.dataset == "maicity"
         if self.maicity:
             self._init_maicity(h)
@@ -194,8 +195,10 @@ class Scene:
     def view_rows(self, f, method):
         pose = self.poses[f - 1] if self.maicity else self.poses[f]
         origin = pose[:3, 3].to(device=self.device, dtype=torch.float64)
+        if self.ray_index == "grid" and self._grid is None:
+            self._grid = ChildGrid(bounds6=self.bounds6)
         return build_view_rows(self.frame_points(f), origin, self.bounds6, self.parent6, method=method,
-                               rule="maicity" if self.maicity else "kitti")
+                               rule="maicity" if self.maicity else "kitti", index=self.ray_index, grid=self._grid)
 
 
 def cache_dir(h, f):

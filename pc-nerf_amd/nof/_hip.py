@@ -73,6 +73,13 @@ _SIGS = {
     "pcnerf_build_train_rays": (c_int, [vp, i64, vp, vp, vp, i64, vp, ctypes.c_double, c_int, vp, vp, vp, vp, vp]),
     "pcnerf_count_view_rows": (c_int, [vp, i64, vp, vp, i64, vp, c_int, c_int, vp, vp, vp]),
     "pcnerf_emit_view_rows": (c_int, [vp, i64, vp, vp, i64, vp, c_int, c_int, vp, vp, vp, vp, vp, vp]),
+    "pcnerf_child_grid_bytes": (c_size, [i64]),
+    "pcnerf_build_child_grid": (c_int, [vp, i64, ctypes.c_double, vp, c_size, vp]),
+    "pcnerf_rays_grid_workspace_bytes": (c_size, [i64]),
+    "pcnerf_build_train_rays_grid": (c_int, [vp, i64, vp, vp, vp, i64, vp, ctypes.c_double, c_int, vp, vp, vp, vp,
+                                             vp, vp]),
+    "pcnerf_count_view_rows_grid": (c_int, [vp, i64, vp, vp, i64, vp, c_int, c_int, vp, vp, vp, vp]),
+    "pcnerf_emit_view_rows_grid": (c_int, [vp, i64, vp, vp, i64, vp, c_int, c_int, vp, vp, vp, vp, vp, vp, vp]),
     "pcnerf_prof_enable": (c_int, [c_int]),
     "pcnerf_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64),
                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),

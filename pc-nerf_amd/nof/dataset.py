@@ -37,6 +37,10 @@ T_VELO2CAM = np.array([[4.276802385584e-04, -9.999672484946e-01, -8.084491683471
                        [0.0, 0.0, 0.0, 1.0]])
 
 CHILD_GROW = 0.025   # ipb2dmapping.py:607, :616 (extend_tmp / extend_tmp2)
+# how the ray tables look children up: "flat" tests every child, "grid" a uniform grid over the child centres
+# (nof.raytable.ChildGrid, one per scene); same rows either way.  "grid" is the default because it measured faster
+# than "flat" on every scene and both row kinds, its build included (profiles/raytable_grid.json).
+DEFAULT_RAY_INDEX = "grid"
 
 # train-frame rules of ipb2dmapping.py:632-640 keyed by frame sparsity (%): keep frame j (0-based loop index,
 # file j+1) for training when rule(j, data_start) holds
@@ -198,14 +202,15 @@ class kitti_dataload(torch.utils.data.Dataset):
 
     Extra keywords: ``device`` (where rays are built and kept), ``sparsity`` (train-frame rule, default the active
     20 % line), ``parent_bounds`` ((lo, hi) overriding the parent cloud's AABB), ``children`` ((min, max) child
-    boxes overriding ``subnerf_path``).  With ``re_loaddata=0`` the cached ``self_rays_<split>.npy`` under
-    ``result_path/save_npy/split_child_nerf2_3`` are loaded; with 1 they are rebuilt and saved there."""
+    boxes overriding ``subnerf_path``), ``ray_index`` ("flat" or "grid": the child lookup of the ray table, see
+    ``nof.raytable``; the rows do not depend on it).  With ``re_loaddata=0`` the cached ``self_rays_<split>.npy``
+    under ``result_path/save_npy/split_child_nerf2_3`` are loaded; with 1 they are rebuilt and saved there."""
 
     def __init__(self, root_dir, split='train', data_start=1439, data_end=1510, cloud_size_val=2048,
                  range_delete_x=2, range_delete_y=1, range_delete_z=0.5, sub_nerf_test_num=3, surface_expand=0.1,
                  over_height=0.168, over_low=-2, interest_x=12, interest_y=12, pose_path=None, subnerf_path=None,
                  parentnerf_path=None, re_loaddata=0, result_path=None, *, device="cuda", sparsity=20,
-                 parent_bounds=None, children=None):
+                 parent_bounds=None, children=None, ray_index=DEFAULT_RAY_INDEX):
         super().__init__()
         self.split, self.cloud_size_val = split, cloud_size_val
         self.device = torch.device(device)
@@ -239,14 +244,16 @@ class kitti_dataload(torch.utils.data.Dataset):
         self.bounds6, self.centers = child_boxes(*(torch.as_tensor(c, dtype=torch.float64).to(self.device)
                                                    for c in children))
         self.sub_nerf_test_num = self.bounds6.shape[0]
-        from .raytable import build_train_rays
+        from .raytable import ChildGrid, build_train_rays
+        grid = ChildGrid(centers=self.centers) if ray_index == "grid" else None   # one per scene, every frame
         rays = []
         for f in frame_ids(data_start, data_end, split, sparsity):
             p = filter_scan(torch.from_numpy(load_frame(root_dir, f)).to(self.device), rd, over_height, over_low)
             w = to_block(p, poses[f])
             w = w[interest_mask(w, positions, interest_x, interest_y)]
             origin = poses[f][:3, 3].to(device=self.device, dtype=torch.float64)
-            rays.append(build_train_rays(w, origin, self.centers, self.bounds6, parent6, surface_expand))
+            rays.append(build_train_rays(w, origin, self.centers, self.bounds6, parent6, surface_expand,
+                                         index=ray_index, grid=grid))
         self.rays = torch.cat(rays) if rays else torch.zeros((0, 15), device=self.device)
         self.ranges = self.rays[:, 14].clone()
         if cache is not None:
@@ -300,13 +307,13 @@ class maicity_dataload(torch.utils.data.Dataset):
     calibration), the parent block given by nerf_{length,width,height}_{min,max}, scans cut to that block, child
     near/far by compute_far_bound0406 (face_rule "0406": every point in a child box yields a row; a ray with fewer
     than two face hits raises IndexError, as in the reference).  val frames: (j+1-3-data_start) % 5 == 0.
-    Extra keywords as kitti_dataload (``device``, ``sparsity``, ``children``)."""
+    Extra keywords as kitti_dataload (``device``, ``sparsity``, ``children``, ``ray_index``)."""
 
     def __init__(self, root_dir, split='train', data_start=0, data_end=36, cloud_size_val=2048, range_delete_x=2,
                  range_delete_y=1, range_delete_z=0.5, sub_nerf_test_num=3, surface_expand=0.1, nerf_length_min=-4.5,
                  nerf_length_max=25.5, nerf_width_min=-12, nerf_width_max=12, nerf_height_min=-2, nerf_height_max=0.5,
                  pose_path=None, subnerf_path=None, re_loaddata=0, result_path=None, *, device="cuda", sparsity=20,
-                 children=None):
+                 children=None, ray_index=DEFAULT_RAY_INDEX):
         super().__init__()
         self.split, self.cloud_size_val = split, cloud_size_val
         self.device = torch.device(device)
@@ -349,12 +356,13 @@ class maicity_dataload(torch.utils.data.Dataset):
         self.bounds6, self.centers = child_boxes(*(torch.as_tensor(c, dtype=torch.float64).to(self.device)
                                                    for c in children))
         self.sub_nerf_test_num = self.bounds6.shape[0]
-        from .raytable import build_train_rays
+        from .raytable import ChildGrid, build_train_rays
+        grid = ChildGrid(centers=self.centers) if ray_index == "grid" else None
         rays = []
         for j in frames:
             origin = torch.tensor(positions[j], dtype=torch.float64, device=self.device)
             rays.append(build_train_rays(frame(j), origin, self.centers, self.bounds6, parent6, surface_expand,
-                                         face_rule="0406"))
+                                         face_rule="0406", index=ray_index, grid=grid))
         self.rays = torch.cat(rays) if rays else torch.zeros((0, 15), device=self.device)
         self.ranges = self.rays[:, 14].clone()
         if cache is not None:
