@@ -58,6 +58,13 @@ int pcnerf_nof_pack_eval(const pcnerf_nof_params* params, float* packed, void* s
  * pcnerf_set_train_math mode 1. */
 int pcnerf_set_eval_math(int mode);
 
+/* Workgroup geometry of the split-fp16 fused queries (the eval query and the store-less train-mode query),
+ * process-wide; returns the previous setting, or -2 for an invalid one.  -1 (default): each query's measured
+ * default.  0..3: bit 0 = one 8-wave workgroup of 96 samples per CU (each wave 2 of a layer's 16 neuron blocks)
+ * instead of two 4-wave workgroups of 48; bit 1 = a 4-slot weight ring instead of 2 slots.  Every geometry computes
+ * the same bits; the setting exists for A/B timing and the bit-identity tests. */
+int pcnerf_set_query_geometry(int geometry);
+
 /* Fused eval-mode query: for every flattened sample g = ray*n_samples + s computes
  *   p_out[g] = NOF(Embedding(o + d*z[g]))        (render.py:18-25 chunk loop, models.py:27-41, :183-203)
  * with o = rays[ray, 0:3], d = rays[ray, 3:6]. */

@@ -252,10 +252,13 @@ __device__ __forceinline__ void eh_split8(const float (&v)[8], eh_f16x8& hi, eh_
 }
 
 // ---- k_nof_eval_h3: the split network (every fp32 product as hi*hi + hi*mid + mid*hi of fp16 parts, fp32
-// accumulation), fused over all 9 layers for a block of 16 EH3_SB samples (48) with the work split over NEURONS: wave w
-// owns neurons 64w .. 64w + 63 of every layer for all the block's samples, so each wave streams only its own neurons'
-// weights from L2 (a 2-slot register ring, one k-step of prefetch, no barrier) and each A operand feeds EH3_SB sample
-// blocks; two workgroups per CU;
+// accumulation), fused over all 9 layers for a block of 16 SB samples with the work split over NEURONS: wave w of NW
+// owns J = 16 / NW neuron blocks (neurons 16 J w .. 16 J (w + 1) - 1) of every layer for all the block's samples, so
+// each wave streams only its own neurons' weights from L2 (an R3-slot register ring, R3 - 1 k-steps of prefetch, no
+// barrier) and each A operand feeds SB sample blocks.  Two geometries, the same 96 samples and two waves per SIMD on
+// a CU either way: <NW 4, SB 3> (two workgroups of 48 samples per CU, each streaming the whole image: the eval query
+// and the store-writing train query) and <NW 8, SB 6> (one workgroup, one pass over the image: the train query);
+// every accumulator sees the same products in the same order in both (the formulas below are for NW = 4: J = 4);
 // the layer outputs go through LDS as the next layer's split B operands ([k-step][sample block][part][lane],
 // 16 KiB per sample block), two barriers per layer.  The encoding lives in LDS as layer 0's split B operands; layer 4 re-splits it
 // (hi + mid is exact in fp32) at the per-sample scale it shares with h3.
@@ -267,6 +270,7 @@ __device__ __forceinline__ void eh_split8(const float (&v)[8], eh_f16x8& hi, eh_
 // Operand maps (16x16x32: lane l = column l & 15, k-group g = l >> 4 holding k = 8g .. 8g + 7; D reg r of lane l =
 // row 4g + r, column l & 15):
 //   accumulator acc[j][sb] reg r, lane l = neuron 64w + 16j + 4g + r of sample 16sb + (l & 15);
+//   (NW = 8: neuron 32w + 16j + 4g + r, and act[w] below)
 //   a layer's output in LDS: act[2w + jp][sb][part][l] = (acc[2jp][sb][0..3], acc[2jp + 1][sb][0..3]) of lane l, so
 //   hidden k-step s, k-group g, element e is input neuron 32s + 16(e >> 2) + 4g + (e & 3) (the image's column map);
 //   the encoding: eb[s][sb][part][l] element e = feature 32s + 8g + e (63: zero padding).
@@ -316,8 +320,17 @@ __global__ void k_pack_eval_h3(NofParamsDev P, float* __restrict__ out) {
 constexpr int EH3_SB = 3;
 constexpr int EH3_WG_PER_CU = 2;
 static_assert(96 % (16 * EH3_SB) == 0, "store_layer_bytes (pcnerf_internal.h) pads a chunk to whole 96-sample blocks");
-// k_nof_eval_h3: weight-ring slots (prefetch distance EH3_RING - 1 k-steps of 32; a 4-slot ring: +7 %)
+// The wide geometry <NW = 8, SB = 6>: the same 96 samples per CU as ONE workgroup of 8 waves, wave w owning neuron
+// blocks 2w, 2w + 1 (J = 2), so a CU streams the weight image once per 96 samples instead of twice; still two waves
+// per SIMD, but the two halves no longer run independent phases.  ~140 KiB of LDS, __launch_bounds__(512, 1).
+constexpr int EH3_SB_WIDE = 6;
+static_assert(96 % (16 * EH3_SB_WIDE) == 0, "store_layer_bytes pads a chunk to whole 96-sample blocks");
+// k_nof_eval_h3: weight-ring slots (prefetch distance R3 - 1 k-steps of 32).  The ring index is pos % R3 with pos a
+// compile-time constant at every call site, which needs every layer of a rolled layer loop to start on the same slot:
+// R3 = 2 and 4 do, 3 would need the layer loops unrolled (not built).  Measurements of the geometries and ring depths:
+// profiles/QUERY_GEOMETRY.md
 constexpr int EH3_RING = 2;
+constexpr int EH3_RING_DEEP = 4;
 // The store-writing train query writes the activation store nontemporal (streamed past L2, which holds the weight
 // image): -3.8 % (profiles/r03n_variants_eval_ntstore.json).  k_nof_eval_h3<true> issues the MFMAs of a product
 // group neuron-block-outer, the eval query sample-block-outer: -0.9 % / -1.4 % and +4.2 % in same-process A/Bs,
@@ -339,14 +352,17 @@ constexpr int EH3_RING = 2;
 // before the BatchNorm fma, whole 32-sample tiles (the store pads a chunk to 96 samples), its raw bias from LDS
 // (loaded one layer ahead): a global bias load there waited for the previous sample block's stores.  Compile-time
 // store + LDS bias: store-writing query -3.3 % (profiles/r04_variants_store_query.json).
-template <bool TR, bool ST = false>
-__global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float* __restrict__ rays, int stride,
+template <bool TR, bool ST = false, int NW = 4, int SB = EH3_SB, int R3 = EH3_RING>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_eval_h3(
+                                                        const float* __restrict__ rays, int stride,
                                                         const float* __restrict__ z, int64_t total, int S,
                                                         const float* __restrict__ ein, const float* __restrict__ W,
                                                         float* __restrict__ p_out, const float* __restrict__ coef,
                                                         int64_t chunk, float* __restrict__ hst, int64_t hst_chunk,
                                                         int64_t hst_layer, int cy0) {
-  constexpr int SB = EH3_SB, NS = 16 * SB, R3 = EH3_RING, D3 = R3 - 1;
+  static_assert(NW == 4 || NW == 8, "waves per workgroup");
+  // J neuron blocks per wave, JP output k-steps per wave, WPG waves per 64-neuron group of occ_out's sum
+  constexpr int NT = 64 * NW, J = 16 / NW, JP = J / 2, WPG = NW / 4, NS = 16 * SB, D3 = R3 - 1;
   constexpr bool ORD = TR;
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
   __shared__ eh_f16x8 act[8][SB][2][64];
@@ -354,7 +370,7 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
   __shared__ int sx0s[NS];
   __shared__ __attribute__((aligned(16))) float sbias[(TR ? 16 : 8) * 256];
   __shared__ float emax[NS];
-  __shared__ float smax[4][NS];   // (eval)
+  __shared__ float smax[NW][NS];   // (eval)
   __shared__ float pdot[4][NS];
   __shared__ float spos[NS][3];
   // TR with the store: the raw biases of two consecutive layers (slot L & 1), each loaded one layer ahead
@@ -385,38 +401,39 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
 #pragma unroll
     for (int L = 0; L < 8; ++L) sxB[L] = __builtin_amdgcn_readfirstlane(L < 7 ? cs[L] : 0);
   }
-  // this wave's A operands of k-step gk: neuron blocks 4w + j, parts hi / mid
-  auto load_w = [&](eh_f16x8 (&d)[4][2], int gk) __attribute__((always_inline)) {
+  // this wave's A operands of k-step gk: neuron blocks J w + j, parts hi / mid
+  auto load_w = [&](eh_f16x8 (&d)[J][2], int gk) __attribute__((always_inline)) {
     // (k-steps past the end reload the last one: unconditional loads keep the ring's registers statically known to
     // the waitcnt pass -- a conditional load made it wait for every load in flight)
     gk = gk < EH3_KSTEPS ? gk : EH3_KSTEPS - 1;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < J; ++j)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) d[j][p] = img[((size_t)(gk * 16 + 4 * w + j) * 2 + p) * 64 + lane];
+      for (int p = 0; p < 2; ++p) d[j][p] = img[((size_t)(gk * 16 + J * w + j) * 2 + p) * 64 + lane];
   };
-  eh_f16x8 wr[R3][4][2];
+  eh_f16x8 wr[R3][J][2];
 #pragma unroll
   for (int k = 0; k < D3; ++k) load_w(wr[k], k);
-  if (storing) {
+  if (storing && (NT == 256 || t < 256)) {
     sbraw[0][t] = W[OFF_BIAS + t];
     sbraw[TR ? 1 : 0][t] = W[OFF_BIAS + 256 + t];
   }
   if (TR) {
     const f32x4_* cf = reinterpret_cast<const f32x4_*>(coef + cy * (size_t)TQ_COEF_FLOATS);
-    f32x4_ cv[4];
+    constexpr int CM = 16 * 256 / 4 / NT;
+    f32x4_ cv[CM];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) cv[m] = cf[t + 256 * m];
+    for (int m = 0; m < CM; ++m) cv[m] = cf[t + NT * m];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int i = 4 * (t + 256 * m), L = i >> 9, isb = (i >> 8) & 1;
+    for (int m = 0; m < CM; ++m) {
+      const int i = 4 * (t + NT * m), L = i >> 9, isb = (i >> 8) & 1;
       const int sxo = sxB[L], sxi = (L == 0 || L == 4) ? 0 : sxB[L - 1];
       const int e = isb ? sxo : sxo - sw[L] - sxi;
-      reinterpret_cast<f32x4_*>(sbias)[t + 256 * m] =
+      reinterpret_cast<f32x4_*>(sbias)[t + NT * m] =
           f32x4_{ldexpf(cv[m][0], e), ldexpf(cv[m][1], e), ldexpf(cv[m][2], e), ldexpf(cv[m][3], e)};
     }
   } else {
-    for (int i = t; i < 8 * 256 / 4; i += 256)
+    for (int i = t; i < 8 * 256 / 4; i += NT)
       reinterpret_cast<f32x4_*>(sbias)[i] = reinterpret_cast<const f32x4_*>(W + OFF_BIAS)[i];
   }
   float* const encf = reinterpret_cast<float*>(&act[0][0][0][0]);   // [sample][65]
@@ -433,7 +450,7 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       encf[t * 65 + 63] = 0.0f;
     }
     __syncthreads();
-    for (int i = t; i < NS * 30; i += 256) {
+    for (int i = t; i < NS * 30; i += NT) {
       const int sm = i / 30, r = i - 30 * sm, k = r / 3, m = r - 3 * k;
       float sv, cv;
       sincosf((float)(1 << k) * spos[sm][m], &sv, &cv);
@@ -479,12 +496,12 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
   int sxl[SB];   // the per-sample scale of the current layer's B operands (this lane's sample of each block)
 #pragma unroll
   for (int sb = 0; sb < SB; ++sb) sxl[sb] = sx0s[16 * sb + li];
-  f32x4_ acc[4][SB];
+  f32x4_ acc[J][SB];
   int gk = 0;
   // one encoding k-step (layers 0 and 4)
   auto kstep_enc = [&](int s, int pos, bool first) __attribute__((always_inline)) {
-    load_w(wr[(pos + D3) & (R3 - 1)], gk + D3);
-    const eh_f16x8 (&wc)[4][2] = wr[pos & (R3 - 1)];
+    load_w(wr[(pos + D3) % R3], gk + D3);
+    const eh_f16x8 (&wc)[J][2] = wr[pos % R3];
     eh_f16x8 bh[SB], bm[SB];
 #pragma unroll
     for (int sb = 0; sb < SB; ++sb) {
@@ -500,23 +517,23 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       }
     }
 #pragma unroll
-    for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+    for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-      for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+      for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
         const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
         acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][0], bm[sb], first ? f32x4_{} : acc[j][sb], 0, 0, 0);
       }
 #pragma unroll
-    for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+    for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-      for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+      for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
         const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
         acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][0], bh[sb], acc[j][sb], 0, 0, 0);
       }
 #pragma unroll
-    for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+    for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-      for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+      for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
         const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
         acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][1], bh[sb], acc[j][sb], 0, 0, 0);
       }
@@ -535,12 +552,12 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int pos = pos0 + s;
-      load_w(wr[(pos + D3) & (R3 - 1)], gk + D3);
-      const eh_f16x8 (&wc)[4][2] = wr[pos & (R3 - 1)];
+      load_w(wr[(pos + D3) % R3], gk + D3);
+      const eh_f16x8 (&wc)[J][2] = wr[pos % R3];
 #pragma unroll
-      for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+      for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-        for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+        for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
           const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
           acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][0], bm[sb], (first && s == 0) ? f32x4_{} : acc[j][sb], 0, 0, 0);
         }
@@ -551,16 +568,16 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+      for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-        for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+        for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
           const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
           acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][0], bh[sb], acc[j][sb], 0, 0, 0);
         }
 #pragma unroll
-      for (int o1 = 0; o1 < (ORD ? 4 : SB); ++o1)
+      for (int o1 = 0; o1 < (ORD ? J : SB); ++o1)
 #pragma unroll
-        for (int o2 = 0; o2 < (ORD ? SB : 4); ++o2) {
+        for (int o2 = 0; o2 < (ORD ? SB : J); ++o2) {
           const int sb = ORD ? o2 : o1, j = ORD ? o1 : o2;
           acc[j][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wc[j][1], bh[sb], acc[j][sb], 0, 0, 0);
         }
@@ -580,8 +597,8 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       const float us = ldexpf(1.0f, -(sw[L] + sxl[sb]));
       float m = 0.0f;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4_ b = *reinterpret_cast<const f32x4_*>(sbias + 256 * L + 64 * w + 16 * j + 4 * g);
+      for (int j = 0; j < J; ++j) {
+        const f32x4_ b = *reinterpret_cast<const f32x4_*>(sbias + 256 * L + 16 * J * w + 16 * j + 4 * g);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const float v = __builtin_fmaf(acc[j][sb][q], us, b[q]);
@@ -594,12 +611,12 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       if (g == 0) smax[w][16 * sb + li] = m;
     }
   };
-  // this wave's outputs as the next layer's B operands (k-steps 2w, 2w + 1), at scale xs per sample block
+  // this wave's outputs as the next layer's B operands (k-steps JP w .. JP w + JP - 1), at scale xs per sample block
   auto split_out = [&](const float (&xs)[SB], auto SC) {
 #pragma unroll
     for (int sb = 0; sb < SB; ++sb)
 #pragma unroll
-      for (int jp = 0; jp < 2; ++jp) {
+      for (int jp = 0; jp < JP; ++jp) {
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -608,8 +625,8 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
         }
         eh_f16x8 hi, mid;
         eh_split8(v, hi, mid);
-        act[2 * w + jp][sb][0][lane] = hi;
-        act[2 * w + jp][sb][1][lane] = mid;
+        act[JP * w + jp][sb][0][lane] = hi;
+        act[JP * w + jp][sb][1][lane] = mid;
       }
   };
   auto epi2 = [&](bool with_e) __attribute__((always_inline)) {
@@ -618,6 +635,8 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
     for (int sb = 0; sb < SB; ++sb) {
       const int sm = 16 * sb + li;
       float m = fmaxf(fmaxf(smax[0][sm], smax[1][sm]), fmaxf(smax[2][sm], smax[3][sm]));
+#pragma unroll
+      for (int k = 4; k < NW; ++k) m = fmaxf(m, smax[k][sm]);   // (a maximum: the order is free)
       if (with_e) m = fmaxf(m, emax[sm]);
       sxl[sb] = eh_scale(m);
       xs[sb] = ldexpf(1.0f, sxl[sb]);
@@ -629,7 +648,7 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
   // 16(q & 1) + (l & 15) of tile q >> 1, q = SB blockIdx.x + sb the 16-sample block within the chunk
   auto store_raw = [&](int L, int sb, int j, float sc) __attribute__((always_inline)) {
     const int64_t q = (int64_t)blockIdx.x * SB + sb, tile = q >> 1;
-    const int n0 = 64 * w + 16 * j + 4 * g;
+    const int n0 = 16 * J * w + 16 * j + 4 * g;
     const f32x4_ b = *reinterpret_cast<const f32x4_*>(&sbraw[TR ? L & 1 : 0][TR ? n0 : 0]);
     const f32x4_ v = {acc[j][sb][0] * sc + b[0], acc[j][sb][1] * sc + b[1], acc[j][sb][2] * sc + b[2],
                       acc[j][sb][3] * sc + b[3]};
@@ -637,7 +656,7 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
     // a uniform layer base and a 32-bit byte offset (launch_train_query checks a layer's region is < 4 GiB): the
     // stores take the scalar-base form, one offset register per sample block
     char* const hb = reinterpret_cast<char*>(hst + (int64_t)cy * hst_chunk + (int64_t)L * hst_layer);
-    const uint32_t off = ((uint32_t)tile * 32u + (uint32_t)(8 * w + (g >> 1))) * 1024u + (uint32_t)sl * 16u +
+    const uint32_t off = ((uint32_t)tile * 32u + (uint32_t)(2 * J * w + (g >> 1))) * 1024u + (uint32_t)sl * 16u +
                          (uint32_t)j * 2048u;
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4_*>(hb + off));
   };
@@ -649,11 +668,11 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
       if (storing) {
         const float sc = ldexpf(1.0f, -(sw[L] + (ps ? sxl[sb] : (L > 0 ? sxB[L - 1] : 0))));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) store_raw(L, sb, j, sc);
+        for (int j = 0; j < J; ++j) store_raw(L, sb, j, sc);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int nb = 64 * w + 16 * j + 4 * g;
+      for (int j = 0; j < J; ++j) {
+        const int nb = 16 * J * w + 16 * j + 4 * g;
         const f32x4_ a = *reinterpret_cast<const f32x4_*>(sbias + 512 * L + nb);
         const f32x4_ b = *reinterpret_cast<const f32x4_*>(sbias + 512 * L + 256 + nb);
 #pragma unroll
@@ -687,11 +706,11 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
   // the next layer's raw bias, loaded at the start of layer L (bnext) and written to its slot before L's epilogue
   float bnext = 0.0f;
   auto bias_load = [&](int L) __attribute__((always_inline)) {
-    if (storing && L < 7) bnext = W[OFF_BIAS + 256 * (L + 1) + t];
+    if (storing && L < 7 && (NT == 256 || t < 256)) bnext = W[OFF_BIAS + 256 * (L + 1) + t];
   };
   auto layer_end = [&](int L) __attribute__((always_inline)) {
     if (TR) {
-      if (storing && L < 7) sbraw[TR ? (L + 1) & 1 : 0][TR ? t : 0] = bnext;
+      if (storing && L < 7 && (NT == 256 || t < 256)) sbraw[TR ? (L + 1) & 1 : 0][TR ? t : 0] = bnext;
       if (L == 4) epi_tr(4, std::true_type{});
       else epi_tr(L, std::false_type{});
       if (L < 7) {
@@ -738,19 +757,37 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
     hidden_ksteps(eh3_start(5) % R3, true);
     layer_end(L);
   }
-  // occ_out: this wave's 64 neurons per sample, then the 4 partial sums in order
+  // occ_out: each 64-neuron group's fma chain per lane and sample block (j, q ascending), the two cross-lane adds,
+  // then the 4 group sums in order.  NW = 4: wave w is group w.  NW = 8: waves 2p, 2p + 1 are group p -- the even
+  // wave runs the chain's first half (neuron blocks 4p, 4p + 1) and hands its running value per lane to the odd wave
+  // through LDS (eb: last read in layer 4, two or more barriers ago), which continues it: the same fmas in the same
+  // order as the 4-wave form
+  auto occ_chain = [&](int sb, float part) __attribute__((always_inline)) {
 #pragma unroll
-  for (int sb = 0; sb < SB; ++sb) {
-    float part = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4_ wv = *reinterpret_cast<const f32x4_*>(W + OFF_WOUT + 64 * w + 16 * j + 4 * g);
+    for (int j = 0; j < J; ++j) {
+      const f32x4_ wv = *reinterpret_cast<const f32x4_*>(W + OFF_WOUT + 16 * J * w + 16 * j + 4 * g);
 #pragma unroll
       for (int q = 0; q < 4; ++q) part = fmaf(wv[q], acc[j][sb][q], part);
     }
-    part += __shfl_xor(part, 16, 64);
-    part += __shfl_xor(part, 32, 64);
-    if (g == 0) pdot[w][16 * sb + li] = part;
+    return part;
+  };
+  float (*const hand)[SB][64] = reinterpret_cast<float (*)[SB][64]>(&eb[0][0][0][0]);
+  static_assert(sizeof(eb) >= 4 * SB * 64 * sizeof(float), "occ_out handover area");
+  if (WPG == 2) {
+    if (!(w & 1)) {
+#pragma unroll
+      for (int sb = 0; sb < SB; ++sb) hand[w >> 1][sb][lane] = occ_chain(sb, 0.0f);
+    }
+    __syncthreads();
+  }
+  if (WPG == 1 || (w & 1)) {
+#pragma unroll
+    for (int sb = 0; sb < SB; ++sb) {
+      float part = occ_chain(sb, WPG == 1 ? 0.0f : hand[w >> 1][sb][lane]);
+      part += __shfl_xor(part, 16, 64);
+      part += __shfl_xor(part, 32, 64);
+      if (g == 0) pdot[w / WPG][16 * sb + li] = part;
+    }
   }
   __syncthreads();
   if (t < NS && s0 + t < send) {
@@ -762,14 +799,36 @@ __global__ __launch_bounds__(256, EH3_WG_PER_CU) void k_nof_eval_h3(const float*
 // Eval-mode MLP arithmetic: 0 = fp32 MFMA (k_nof_eval), 1 = split fp16, 3 products (k_nof_eval_h3, default).
 static int g_eval_math = 1;
 
+// Geometry of k_nof_eval_h3 for the eval query and the store-less train query (pcnerf_set_query_geometry):
+// bit 0 = the 8-wave workgroup of 96 samples, bit 1 = the 4-slot weight ring; -1 = each form's measured default.
+// Every geometry computes the same bits (tests/test_query_geometry_gpu.py).
+static int g_query_geometry = -1;
+// The defaults, from the interleaved A/B against the parent commit (profiles/QUERY_GEOMETRY.md): the train query
+// takes the 8-wave form (config 2 forward 83.31 -> 80.02 ms, L2 read requests halved, clock up), the eval query stays
+// on the 4-wave form (8 waves: +0.3 %, inside the spread); the 4-slot ring lost in both geometries and both queries.
+constexpr int EH3_GEOM_EVAL = 0, EH3_GEOM_TRAIN = 1;
+
+// launches k_nof_eval_h3<TR, false> in geometry geom: `rows` grid rows (BatchNorm chunks) of `span` samples each
+template <bool TR, typename... Args>
+static void launch_h3(int geom, int64_t span, unsigned rows, hipStream_t s, Args... args) {
+  const bool wide = geom & 1, deep = geom & 2;
+  const int64_t ns = 16 * (wide ? EH3_SB_WIDE : EH3_SB);
+  const dim3 grid((unsigned)((span + ns - 1) / ns), rows), block(wide ? 512 : 256);
+  if (wide && deep)
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING_DEEP>), grid, block, 0, s, args...);
+  else if (wide)
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING>), grid, block, 0, s, args...);
+  else if (deep)
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING_DEEP>), grid, block, 0, s, args...);
+  else
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING>), grid, block, 0, s, args...);
+}
+
 static void launch_eval(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
                         const float* W, float* p_out, hipStream_t s) {
   if (g_eval_math == 1) {
-    const int64_t ns = 16 * EH3_SB;
-    hipLaunchKernelGGL(k_nof_eval_h3<false>,
-                       dim3((unsigned)((total + ns - 1) / ns)), dim3(256), 0,
-                       s, rays, stride, z, total, S, ein, W, p_out, nullptr, (int64_t)0, nullptr, (int64_t)0,
-                       (int64_t)0, 0);
+    launch_h3<false>(g_query_geometry < 0 ? EH3_GEOM_EVAL : g_query_geometry, total, 1u, s, rays, stride, z, total, S,
+                     ein, W, p_out, (const float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
   } else {
     const int64_t blocks = ((total + 31) / 32 + 3) / 4;
     hipLaunchKernelGGL(k_nof_eval, dim3((unsigned)blocks), dim3(256), 0, s, rays, stride, z, total, S, ein, W,
@@ -942,8 +1001,9 @@ void launch_train_query(const float* rays, int stride, const float* z, int64_t t
     hipLaunchKernelGGL((k_nof_eval_h3<true, true>), dim3((unsigned)per, (unsigned)Cs), dim3(256), 0, s, rays,
                        stride, z, total, S, ein, img, p_out, coef, chunk, hst, hst_chunk, hst_layer, 0);
   if (C > Cs)
-    hipLaunchKernelGGL((k_nof_eval_h3<true, false>), dim3((unsigned)per, (unsigned)(C - Cs)), dim3(256), 0, s, rays,
-                       stride, z, total, S, ein, img, p_out, coef, chunk, nullptr, (int64_t)0, (int64_t)0, (int)Cs);
+    launch_h3<true>(g_query_geometry < 0 ? EH3_GEOM_TRAIN : g_query_geometry, std::min(chunk, total),
+                    (unsigned)(C - Cs), s, rays, stride, z, total, S, ein, img, p_out, coef, chunk, (float*)nullptr,
+                    (int64_t)0, (int64_t)0, (int)Cs);
 }
 
 void launch_fold_logits(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
@@ -1066,6 +1126,17 @@ extern "C" int pcnerf_nof_forward_eval(const float* emb, int64_t n, const float*
   PCN_API_END
 }
 
+
+extern "C" int pcnerf_set_query_geometry(int geometry) {
+  if (geometry < -1 || geometry > 3) {
+    pcn::set_error("pcnerf_set_query_geometry: geometry must be -1 (default) or 0..3 (bit 0: 8-wave workgroup, "
+                   "bit 1: 4-slot weight ring)");
+    return -2;
+  }
+  const int prev = pcn::g_query_geometry;
+  pcn::g_query_geometry = geometry;
+  return prev;
+}
 
 extern "C" int pcnerf_set_eval_math(int mode) {
   if (mode < 0 || mode > 1) {

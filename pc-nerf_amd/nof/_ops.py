@@ -194,6 +194,20 @@ if os.environ.get("PCNERF_EVAL_MATH"):
     set_eval_math(os.environ["PCNERF_EVAL_MATH"])
 
 
+def set_query_geometry(geometry: int) -> int:
+    """Workgroup geometry of the split-fp16 fused queries (pcnerf_set_query_geometry): -1 each query's default,
+    0..3 = bit 0 the 8-wave 96-sample workgroup, bit 1 the 4-slot weight ring.  Same bits in every geometry; for
+    A/B timing and tests.  Returns the previous setting."""
+    prev = H.lib().pcnerf_set_query_geometry(int(geometry))
+    if prev < -1:
+        raise ValueError(H.lib().pcnerf_last_error().decode())
+    return prev
+
+
+if os.environ.get("PCNERF_QUERY_GEOMETRY"):
+    set_query_geometry(int(os.environ["PCNERF_QUERY_GEOMETRY"]))
+
+
 # render_rays' depth2 (render.py:598-600) ranks the last sample in argsort(weights, descending=True); where weights
 # tie exactly (every weight after an opaque sample is 0) the order of equal keys decides.  "stable" (default): the
 # order torch's sort gives on the GPU, where the reference runs render_rays (it moves the draws to cuda:0,
