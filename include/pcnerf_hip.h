@@ -238,6 +238,34 @@ int pcnerf_nof_query_train_backward_remat(const float* rays, int64_t n_rays, int
                                           int n_samples, int64_t chunk, const pcnerf_nof_params* params, float eps,
                                           const float* grad_logit, void* state, size_t state_bytes, void* workspace,
                                           size_t workspace_bytes, const pcnerf_nof_grads* grads, void* stream);
+/* ---------------------------------------------------------------- fused queries on explicit sample positions
+ * The queries above with a third sample source: pts (n, 3) float32, contiguous, the flattened ray-major sample
+ * positions, each taken verbatim -- they need not lie on any ray (jittered or warped samples, a voxel grid).  The
+ * encoding stays fused (no (n, 63) embedding is written) and the arithmetic is the ray-sourced queries': on
+ * pts = fl(o + fl(d*z)) the results are bit-identical.  BatchNorm chunk c covers samples [c*chunk, min((c+1)*chunk, n)).
+ * pcnerf_nof_points_eval: p_out[g] = NOF(Embedding(pts[g])) in eval mode -- inference_val's / inference's /
+ *   inference_0525_2's chunk loop over the caller's samples_xy (render.py:18-25; models.py:27-41, :183-203).  Eval
+ *   math 1 only (under eval math 0: pcnerf_embed + pcnerf_nof_forward_eval).
+ * pcnerf_nof_points_train_fused: inference_train's train-mode chunk loop (render.py:44-51; models.py:27-41, :183-203
+ *   with BatchNorm batch statistics per chunk, running stats updated chunk by chunk), forward only; `state` is
+ *   pcnerf_nof_train_fused_bytes(n, chunk) bytes of scratch.
+ * pcnerf_nof_points_train_fused_state: the same, keeping the pcnerf_nof_train_fold_bytes(n, chunk) `state` for the
+ *   backward.  pcnerf_nof_train_bn_stats reads either state as it reads a ray query's.
+ * pcnerf_nof_points_train_backward_remat: the autograd of that loop to the parameters, as
+ *   pcnerf_nof_query_train_backward_remat: `state` is consumed, `workspace` is
+ *   pcnerf_nof_backward_workspace_bytes(chunk) bytes, train math 1 (f16x2_3) only, gradients are ADDED to `grads`.
+ *   No gradient is taken with respect to pts. */
+int pcnerf_nof_points_eval(const float* pts, int64_t n, const float* packed, float* p_out, void* stream);
+int pcnerf_nof_points_train_fused(const float* pts, int64_t n, int64_t chunk, const pcnerf_nof_params* params,
+                                  float momentum, float eps, void* state, size_t state_bytes, float* p_out,
+                                  void* stream);
+int pcnerf_nof_points_train_fused_state(const float* pts, int64_t n, int64_t chunk, const pcnerf_nof_params* params,
+                                        float momentum, float eps, void* state, size_t state_bytes, float* p_out,
+                                        void* stream);
+int pcnerf_nof_points_train_backward_remat(const float* pts, int64_t n, int64_t chunk,
+                                           const pcnerf_nof_params* params, float eps, const float* grad_logit,
+                                           void* state, size_t state_bytes, void* workspace, size_t workspace_bytes,
+                                           const pcnerf_nof_grads* grads, void* stream);
 /* NOF.forward(emb) in train mode on an embedded batch of n rows (one chunk), the same way. */
 int pcnerf_nof_forward_train_fused(const float* emb, int64_t n, const pcnerf_nof_params* params, float momentum,
                                    float eps, void* state, size_t state_bytes, float* p_out, void* stream);

@@ -352,7 +352,9 @@ constexpr int EH3_RING_DEEP = 4;
 // before the BatchNorm fma, whole 32-sample tiles (the store pads a chunk to 96 samples), its raw bias from LDS
 // (loaded one layer ahead): a global bias load there waited for the previous sample block's stores.  Compile-time
 // store + LDS bias: store-writing query -3.3 % (profiles/r04_variants_store_query.json).
-template <bool TR, bool ST = false, int NW = 4, int SB = EH3_SB, int R3 = EH3_RING>
+// PT (the explicit-point source, compile-time: the ray / ein forms are the code they were): `rays` holds the (total, 3)
+// sample positions, read verbatim (load_point); stride, z, S and ein are not read.
+template <bool TR, bool ST = false, int NW = 4, int SB = EH3_SB, int R3 = EH3_RING, bool PT = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_eval_h3(
                                                         const float* __restrict__ rays, int stride,
                                                         const float* __restrict__ z, int64_t total, int S,
@@ -361,6 +363,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
                                                         int64_t chunk, float* __restrict__ hst, int64_t hst_chunk,
                                                         int64_t hst_layer, int cy0) {
   static_assert(NW == 4 || NW == 8, "waves per workgroup");
+  static_assert(!(PT && ST), "the activation store is not built for the point source");
   // J neuron blocks per wave, JP output k-steps per wave, WPG waves per 64-neuron group of occ_out's sum
   constexpr int NT = 64 * NW, J = 16 / NW, JP = J / 2, WPG = NW / 4, NS = 16 * SB, D3 = R3 - 1;
   constexpr bool ORD = TR;
@@ -383,7 +386,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   if (s0 >= send) return;   // (the last chunk's surplus blocks; uniform over the block, before any barrier)
   constexpr bool storing = TR && ST;
   float rz = 0.0f, rr[6] = {};
-  if (!ein && t < NS) {
+  if constexpr (PT) {
+    if (t < NS) {
+      int64_t gs = s0 + t;
+      if (gs >= send) gs = send - 1;
+      float p[3];
+      load_point(rays, gs, p);
+#pragma unroll
+      for (int m = 0; m < 3; ++m) rr[m] = p[m];
+    }
+  } else if (!ein && t < NS) {
     int64_t gs = s0 + t;
     if (gs >= send) gs = send - 1;
     const float* r = rays + ray_of(gs, S) * stride;
@@ -438,10 +450,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   }
   float* const encf = reinterpret_cast<float*>(&act[0][0][0][0]);   // [sample][65]
   static_assert(sizeof(act) >= NS * 65 * sizeof(float), "encoding staging area");
-  if (!ein) {
+  if (PT || !ein) {
     if (t < NS) {
       float p[3];
-      sample_point(rr, rz, p);
+      if constexpr (PT) p[0] = rr[0], p[1] = rr[1], p[2] = rr[2];
+      else sample_point(rr, rz, p);
 #pragma unroll
       for (int m = 0; m < 3; ++m) {
         spos[t][m] = p[m];
@@ -461,7 +474,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   }
   if (t < NS) {   // one sample's encoding per thread, stored in B order
     float f[64];
-    if (ein) {
+    if (!PT && ein) {
       int64_t gs = s0 + t;
       if (gs >= send) gs = send - 1;
 #pragma unroll
@@ -809,26 +822,34 @@ static int g_query_geometry = -1;
 constexpr int EH3_GEOM_EVAL = 0, EH3_GEOM_TRAIN = 1;
 
 // launches k_nof_eval_h3<TR, false> in geometry geom: `rows` grid rows (BatchNorm chunks) of `span` samples each
-template <bool TR, typename... Args>
+// (PT: the point source, the positions in the kernel's `rays` argument)
+template <bool TR, bool PT, typename... Args>
 static void launch_h3(int geom, int64_t span, unsigned rows, hipStream_t s, Args... args) {
   const bool wide = geom & 1, deep = geom & 2;
   const int64_t ns = 16 * (wide ? EH3_SB_WIDE : EH3_SB);
   const dim3 grid((unsigned)((span + ns - 1) / ns), rows), block(wide ? 512 : 256);
   if (wide && deep)
-    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING_DEEP>), grid, block, 0, s, args...);
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING_DEEP, PT>), grid, block, 0, s, args...);
   else if (wide)
-    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING>), grid, block, 0, s, args...);
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 8, EH3_SB_WIDE, EH3_RING, PT>), grid, block, 0, s, args...);
   else if (deep)
-    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING_DEEP>), grid, block, 0, s, args...);
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING_DEEP, PT>), grid, block, 0, s, args...);
   else
-    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING>), grid, block, 0, s, args...);
+    hipLaunchKernelGGL((k_nof_eval_h3<TR, false, 4, EH3_SB, EH3_RING, PT>), grid, block, 0, s, args...);
 }
 
+// pts != NULL: the explicit-point source (eval math 1 only; the caller checks)
 static void launch_eval(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
-                        const float* W, float* p_out, hipStream_t s) {
-  if (g_eval_math == 1) {
-    launch_h3<false>(g_query_geometry < 0 ? EH3_GEOM_EVAL : g_query_geometry, total, 1u, s, rays, stride, z, total, S,
-                     ein, W, p_out, (const float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
+                        const float* W, float* p_out, hipStream_t s, const float* pts = nullptr) {
+  if (pts) {
+    if (g_eval_math != 1) throw std::runtime_error("point query: needs eval math 1 (split fp16)");
+    launch_h3<false, true>(g_query_geometry < 0 ? EH3_GEOM_EVAL : g_query_geometry, total, 1u, s, pts, 3,
+                           (const float*)nullptr, total, 1, (const float*)nullptr, W, p_out, (const float*)nullptr,
+                           (int64_t)0, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
+  } else if (g_eval_math == 1) {
+    launch_h3<false, false>(g_query_geometry < 0 ? EH3_GEOM_EVAL : g_query_geometry, total, 1u, s, rays, stride, z,
+                            total, S, ein, W, p_out, (const float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0,
+                            (int64_t)0, 0);
   } else {
     const int64_t blocks = ((total + 31) / 32 + 3) / 4;
     hipLaunchKernelGGL(k_nof_eval, dim3((unsigned)blocks), dim3(256), 0, s, rays, stride, z, total, S, ein, W,
@@ -988,8 +1009,9 @@ void pack_train_query(const NofParamsDev& P, float* img, hipStream_t s) {
 
 void launch_train_query(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
                         const float* img, const float* coef, int64_t chunk, float* p_out, hipStream_t s,
-                        float* hst, int64_t hst_chunk, int64_t hst_layer, int64_t store_chunks) {
+                        float* hst, int64_t hst_chunk, int64_t hst_layer, int64_t store_chunks, const float* pts) {
   const int64_t C = (total + chunk - 1) / chunk;
+  if (pts && hst) throw std::runtime_error("train query: no activation store with the point source");
   const int64_t ns = 16 * EH3_SB;
   const int64_t per = (std::min(chunk, total) + ns - 1) / ns;
   if (C >= 65536 || per >= ((int64_t)1 << 31)) throw std::runtime_error("train query: too many chunks / samples");
@@ -1000,10 +1022,14 @@ void launch_train_query(const float* rays, int stride, const float* z, int64_t t
   if (Cs > 0)
     hipLaunchKernelGGL((k_nof_eval_h3<true, true>), dim3((unsigned)per, (unsigned)Cs), dim3(256), 0, s, rays,
                        stride, z, total, S, ein, img, p_out, coef, chunk, hst, hst_chunk, hst_layer, 0);
-  if (C > Cs)
-    launch_h3<true>(g_query_geometry < 0 ? EH3_GEOM_TRAIN : g_query_geometry, std::min(chunk, total),
-                    (unsigned)(C - Cs), s, rays, stride, z, total, S, ein, img, p_out, coef, chunk, (float*)nullptr,
-                    (int64_t)0, (int64_t)0, (int)Cs);
+  if (pts)
+    launch_h3<true, true>(g_query_geometry < 0 ? EH3_GEOM_TRAIN : g_query_geometry, std::min(chunk, total),
+                          (unsigned)C, s, pts, 3, (const float*)nullptr, total, 1, (const float*)nullptr, img, p_out,
+                          coef, chunk, (float*)nullptr, (int64_t)0, (int64_t)0, 0);
+  else if (C > Cs)
+    launch_h3<true, false>(g_query_geometry < 0 ? EH3_GEOM_TRAIN : g_query_geometry, std::min(chunk, total),
+                           (unsigned)(C - Cs), s, rays, stride, z, total, S, ein, img, p_out, coef, chunk,
+                           (float*)nullptr, (int64_t)0, (int64_t)0, (int)Cs);
 }
 
 void launch_fold_logits(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
@@ -1111,6 +1137,23 @@ extern "C" int pcnerf_nof_query_eval(const float* rays, int64_t n_rays, int ray_
     launch_eval(rays, ray_stride, z, total, n_samples, nullptr, packed, p_out, (hipStream_t)stream);
   }
   PCN_LAUNCH_CHECK("pcnerf_nof_query_eval");
+  PCN_API_END
+}
+
+extern "C" int pcnerf_nof_points_eval(const float* pts, int64_t n, const float* packed, float* p_out, void* stream) {
+  PCN_API_BEGIN
+  PCN_CHECK(pts && packed && p_out, "pcnerf_nof_points_eval: null argument");
+  PCN_CHECK(n > 0, "pcnerf_nof_points_eval: empty input");
+  const int64_t blocks = ((n + 31) / 32 + 3) / 4;
+  PCN_CHECK(blocks < (int64_t)1 << 31, "pcnerf_nof_points_eval: too many samples for one launch");
+  PCN_CHECK(g_eval_math == 1, "pcnerf_nof_points_eval: needs eval math 1 (split fp16); under eval math 0 embed the "
+                              "points (pcnerf_embed) and call pcnerf_nof_forward_eval");
+  {
+    // algorithmic work: 982,528 FLOP per sample; bytes: the position in, p out, network image
+    ProfScope ps((hipStream_t)stream, PT_EVAL_QUERY, 982528.0 * (double)n, 16.0 * (double)n + 4.0 * EVAL_F32_FLOATS);
+    launch_eval(nullptr, 0, nullptr, n, 1, nullptr, packed, p_out, (hipStream_t)stream, pts);
+  }
+  PCN_LAUNCH_CHECK("pcnerf_nof_points_eval");
   PCN_API_END
 }
 

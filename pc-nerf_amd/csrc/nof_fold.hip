@@ -112,24 +112,28 @@ static FoldDev fold_dev(const FoldLayout& L, void* state) {
   return F;
 }
 
-struct SampleSrc {   // the query's flattened ray-major samples (rays + z) or an embedded batch (ein)
+// the query's flattened ray-major samples (rays + z), an embedded batch (ein) or explicit positions (pts, (total, 3))
+struct SampleSrc {
   const float* rays;
   int stride;
   const float* z;
   int S;
   const float* ein;
   int64_t total, chunk;
+  const float* pts = nullptr;
 };
 
+// (PT: the explicit-point source, a compile-time choice -- see sample_pos)
+template <bool PT>
 __device__ __forceinline__ void sample_enc(const SampleSrc& q, int64_t g, float (&f)[64]) {
-  if (q.ein) {
+  if (!PT && q.ein) {
     const float* r = q.ein + g * 63;
 #pragma unroll
     for (int k = 0; k < 63; ++k) f[k] = r[k];
     f[63] = 0.0f;
   } else {
     float p[3];
-    sample_point(q.rays + ray_of(g, q.S) * q.stride, q.z[g], p);
+    sample_pos<PT>(q.rays, q.stride, q.z, q.S, q.pts, g, p);
     encode_full(p, f);
   }
 }
@@ -156,14 +160,16 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 constexpr int TM_P = 72;
 
+template <bool PT = false>
 __global__ __launch_bounds__(256) void k_tf_moments(SampleSrc q, FoldDev F) {
+  if constexpr (PT) q.ein = nullptr;
   __shared__ __attribute__((aligned(16))) _Float16 th[4][2][64 * TM_P];
   __shared__ float sh0[64];
   const int c = blockIdx.y, w = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t c0 = (int64_t)c * q.chunk, n = chunk_len(q, c);
   if (tid == 0) {
     float f[64];
-    sample_enc(q, c0, f);
+    sample_enc<PT>(q, c0, f);
 #pragma unroll
     for (int k = 0; k < 63; ++k) sh0[k] = f[k];
     sh0[63] = 0.0f;
@@ -191,7 +197,7 @@ __global__ __launch_bounds__(256) void k_tf_moments(SampleSrc q, FoldDev F) {
       if (ok)
         for (int f = 0; f < 63; ++f) dm = fmaxf(dm, fabsf(r[f] - sh0[f]));
     } else if (ok) {
-      sample_point(q.rays + ray_of(c0 + i, q.S) * q.stride, q.z[c0 + i], p);
+      sample_pos<PT>(q.rays, q.stride, q.z, q.S, q.pts, c0 + i, p);
 #pragma unroll
       for (int m = 0; m < 3; ++m) dm = fmaxf(dm, fabsf(p[m] - sh0[m]));
     }
@@ -575,8 +581,10 @@ __device__ __forceinline__ float fold_logit_grad(const float* __restrict__ g, co
 // grid (wpc, C), 256 threads: sum g_s d_s (d as in k_tf_moments, fp32 here; d_63 = 1).  Each wave stages 64
 // samples' d as a [sample][feature] fp32 tile (one lane per sample, its encoding written as computed) and g in
 // LDS; then lane f accumulates sum_s g_s d_s[f] over the tile in float64 (exact products, one register).
+template <bool PT = false>
 __global__ __launch_bounds__(256) void k_tf_gmoments(SampleSrc q, FoldDev F, const float* __restrict__ g,
                                                      const float* __restrict__ p) {
+  if constexpr (PT) q.ein = nullptr;
   __shared__ float tile[4][64 * 65];
   __shared__ float gs[4][64];
   __shared__ float sh0[64];
@@ -599,7 +607,7 @@ __global__ __launch_bounds__(256) void k_tf_gmoments(SampleSrc q, FoldDev F, con
       for (int f = 0; f < 63; ++f) put(f, r[f]);
     } else {
       float pt[3] = {0.0f, 0.0f, 0.0f};
-      if (ok) sample_point(q.rays + ray_of(c0 + i, q.S) * q.stride, q.z[c0 + i], pt);
+      if (ok) sample_pos<PT>(q.rays, q.stride, q.z, q.S, q.pts, c0 + i, pt);
 #pragma unroll
       for (int m = 0; m < 3; ++m) put(m, pt[m]);
 #pragma unroll 2
@@ -857,7 +865,7 @@ static void fold_forward(const SampleSrc& q, const pcnerf_nof_params* params, fl
   {
     // algorithmic work per sample: the encoding + 3 x 32 x 32 x 2 flops per k-step pair; bytes: z in, ray rows
     ProfScope ps(s, PT_FOLD_MOMENTS, 6144.0 * (double)q.total, 4.0 * (double)q.total);
-    hipLaunchKernelGGL(k_tf_moments, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F);
+    hipLaunchKernelGGL(k_tf_moments<false>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F);
   }
   {
     ProfScope ps(s, PT_FOLD_ALGEBRA, 0.0, 0.0);
@@ -900,7 +908,8 @@ static void fused_forward(const SampleSrc& q, const pcnerf_nof_params* params, f
   pack_train_query(P, F.img, s);
   {
     ProfScope ps(s, PT_FOLD_MOMENTS, 6144.0 * (double)q.total, 4.0 * (double)q.total);
-    hipLaunchKernelGGL(k_tf_moments, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F);
+    if (q.pts) hipLaunchKernelGGL(k_tf_moments<true>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F);
+    else hipLaunchKernelGGL(k_tf_moments<false>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F);
   }
   {
     ProfScope ps(s, PT_FOLD_ALGEBRA, 0.0, 0.0);
@@ -922,7 +931,7 @@ static void fused_forward(const SampleSrc& q, const pcnerf_nof_params* params, f
     const int64_t sc = store ? std::min<int64_t>(store_chunks, F.C) : 0;
     const size_t cb = pcnerf_nof_store_bytes(q.chunk), lb = store_layer_bytes(q.chunk);
     launch_train_query(q.rays, q.stride, q.z, q.total, q.S, q.ein, F.img, F.coef, q.chunk, p_out, s,
-                       sc > 0 ? static_cast<float*>(store) : nullptr, (int64_t)(cb / 4), (int64_t)(lb / 4), sc);
+                       sc > 0 ? static_cast<float*>(store) : nullptr, (int64_t)(cb / 4), (int64_t)(lb / 4), sc, q.pts);
     if (sc > 0)
       hipLaunchKernelGGL(k_tf_store_stats, dim3(8, (unsigned)sc), dim3(256), 0, s, F, q, static_cast<char*>(store),
                          cb, 8 * lb);
@@ -949,7 +958,7 @@ static void fold_backward(const SampleSrc& q, const pcnerf_nof_params* params, f
   const FoldDev F = fold_dev(Lo, state);
   {
     ProfScope ps(s, PT_FOLD_MOMENTS, 126.0 * (double)q.total, 8.0 * (double)q.total);
-    hipLaunchKernelGGL(k_tf_gmoments, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F, g, p);
+    hipLaunchKernelGGL(k_tf_gmoments<false>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F, g, p);
   }
   ProfScope ps(s, PT_FOLD_ALGEBRA, 0.0, 0.0);
   hipLaunchKernelGGL(k_tf_bwd_out, dim3(4, (unsigned)F.C), dim3(256), 0, s, P, F);
@@ -970,15 +979,19 @@ static void fold_backward(const SampleSrc& q, const pcnerf_nof_params* params, f
 // statistics -- no weight gradient (the per-sample passes compute those as written).
 FoldBnBwd fold_bn_backward(const float* rays, int stride, const float* z, int S, int64_t total, int64_t chunk,
                            const NofParamsDev& P, const float* g_logit, void* state, size_t state_bytes,
-                           hipStream_t s) {
-  const SampleSrc q{rays, stride, z, S, nullptr, total, std::min(chunk, total)};
+                           hipStream_t s, const float* pts) {
+  const SampleSrc q{rays, stride, z, S, nullptr, total, std::min(chunk, total), pts};
   const FoldLayout Lo = fold_layout(q.total, q.chunk);
   PCN_CHECK(state_bytes >= Lo.doubles * sizeof(double), "train backward: fold state buffer too small");
   const FoldDev F = fold_dev(Lo, state);
   {
     ProfScope ps(s, PT_FOLD_MOMENTS, 126.0 * (double)q.total, 8.0 * (double)q.total);
-    hipLaunchKernelGGL(k_tf_gmoments, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F, g_logit,
-                       (const float*)nullptr);
+    if (pts)
+      hipLaunchKernelGGL(k_tf_gmoments<true>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F, g_logit,
+                         (const float*)nullptr);
+    else
+      hipLaunchKernelGGL(k_tf_gmoments<false>, dim3(F.wpc, (unsigned)F.C), dim3(256), 0, s, q, F, g_logit,
+                         (const float*)nullptr);
   }
   ProfScope ps(s, PT_FOLD_ALGEBRA, 0.0, 0.0);
   hipLaunchKernelGGL(k_tf_bwd_out, dim3(4, (unsigned)F.C), dim3(256), 0, s, P, F);
@@ -1070,6 +1083,38 @@ extern "C" int pcnerf_nof_query_train_fused_state(const float* rays, int64_t n_r
   const SampleSrc q{rays, ray_stride, z, n_samples, nullptr, total, std::min(chunk, total)};
   fused_forward(q, params, momentum, eps, state, state_bytes, p_out, (hipStream_t)stream, nullptr, 0, true);
   PCN_LAUNCH_CHECK("pcnerf_nof_query_train_fused_state");
+  PCN_API_END
+}
+
+// The two fused train queries above on explicit sample positions (render.py:44-51 on the caller's samples_xy).
+static void points_train_checks(const char* who, const float* pts, int64_t n, int64_t chunk,
+                                const pcnerf_nof_params* params, void* state, float* p_out) {
+  const std::string w(who);
+  PCN_CHECK(pts && params && state && p_out, w + ": null argument");
+  PCN_CHECK(n > 0 && chunk > 0, w + ": empty input");
+  // one grid row per chunk of 48-sample blocks (launch_train_query's limit, checked here before any launch)
+  PCN_CHECK((std::min(chunk, n) + 47) / 48 < (int64_t)1 << 31, w + ": too many samples for one launch");
+}
+
+extern "C" int pcnerf_nof_points_train_fused(const float* pts, int64_t n, int64_t chunk,
+                                             const pcnerf_nof_params* params, float momentum, float eps, void* state,
+                                             size_t state_bytes, float* p_out, void* stream) {
+  PCN_API_BEGIN
+  points_train_checks("pcnerf_nof_points_train_fused", pts, n, chunk, params, state, p_out);
+  const SampleSrc q{nullptr, 0, nullptr, 1, nullptr, n, std::min(chunk, n), pts};
+  fused_forward(q, params, momentum, eps, state, state_bytes, p_out, (hipStream_t)stream);
+  PCN_LAUNCH_CHECK("pcnerf_nof_points_train_fused");
+  PCN_API_END
+}
+
+extern "C" int pcnerf_nof_points_train_fused_state(const float* pts, int64_t n, int64_t chunk,
+                                                   const pcnerf_nof_params* params, float momentum, float eps,
+                                                   void* state, size_t state_bytes, float* p_out, void* stream) {
+  PCN_API_BEGIN
+  points_train_checks("pcnerf_nof_points_train_fused_state", pts, n, chunk, params, state, p_out);
+  const SampleSrc q{nullptr, 0, nullptr, 1, nullptr, n, std::min(chunk, n), pts};
+  fused_forward(q, params, momentum, eps, state, state_bytes, p_out, (hipStream_t)stream, nullptr, 0, true);
+  PCN_LAUNCH_CHECK("pcnerf_nof_points_train_fused_state");
   PCN_API_END
 }
 

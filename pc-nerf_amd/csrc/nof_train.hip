@@ -1551,16 +1551,18 @@ static StoreChunk store_chunk(const void* store, int64_t chunk, int64_t ci) {
 // and the layer-0 moments scale per sample / per unit and have no such limit.  Before any launch, one pass over
 // the call's sample positions (sample_point's arithmetic, or the embedded batch's xyz columns) is read back and
 // the call raises instead of returning NaN.
+template <bool PT = false>   // PT: the explicit-point source (pts; the bound is simply max |pts|)
 __global__ __launch_bounds__(256) void k_pos_bound(const float* __restrict__ rays, int stride,
                                                    const float* __restrict__ z, int S, const float* __restrict__ ein,
-                                                   int64_t total, unsigned* __restrict__ out) {
+                                                   int64_t total, unsigned* __restrict__ out,
+                                                   const float* __restrict__ pts) {
   float m = 0.0f;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
     float p[3];
-    if (ein) {
+    if (!PT && ein) {
       p[0] = ein[g * 63], p[1] = ein[g * 63 + 1], p[2] = ein[g * 63 + 2];
     } else {
-      sample_point(rays + ray_of(g, S) * stride, z[g], p);
+      sample_pos<PT>(rays, stride, z, S, pts, g, p);
     }
     m = fmaxf(m, fmaxf(fabsf(p[0]), fmaxf(fabsf(p[1]), fabsf(p[2]))));   // fmaxf drops NaN positions
   }
@@ -1573,10 +1575,15 @@ __global__ __launch_bounds__(256) void k_pos_bound(const float* __restrict__ ray
 }
 
 static void pos_bound_async(const float* rays, int stride, const float* z, int S, const float* ein, int64_t total,
-                            unsigned* dev, hipStream_t s) {
+                            unsigned* dev, hipStream_t s, const float* pts = nullptr) {
   PCN_HIP(hipMemsetAsync(dev, 0, sizeof(unsigned), s));
   const int64_t blocks = std::min<int64_t>(512, (total + 255) / 256);
-  hipLaunchKernelGGL(k_pos_bound, dim3((unsigned)blocks), dim3(256), 0, s, rays, stride, z, S, ein, total, dev);
+  if (pts)
+    hipLaunchKernelGGL(k_pos_bound<true>, dim3((unsigned)blocks), dim3(256), 0, s, rays, stride, z, S, ein, total, dev,
+                       pts);
+  else
+    hipLaunchKernelGGL(k_pos_bound<false>, dim3((unsigned)blocks), dim3(256), 0, s, rays, stride, z, S, ein, total,
+                       dev, pts);
 }
 
 static void check_split_range(const float* rays, int stride, const float* z, int S, const float* ein, int64_t total,
@@ -3255,11 +3262,13 @@ __global__ __launch_bounds__(256) void k_remat_pimg(FoldBnBwd F, const unsigned*
 // LDS and written as whole 16-byte lanes (1 KiB per wave store).  Block 0 also zeroes k_g7's |g_7| slots (gm7) for
 // this chunk (the previous chunk's layer 7 has read them: stream order).
 constexpr int RE_TILES = 4;
+template <bool PT = false>   // PT: the explicit-point source (pts)
 __global__ __launch_bounds__(32 * RE_TILES) void k_remat_enc(const float* __restrict__ rays, int stride,
                                                            const float* __restrict__ z, int S, int64_t c0, int64_t n,
                                                            const double* __restrict__ eb,
                                                            const unsigned* __restrict__ pbound,
-                                                           char* __restrict__ out, unsigned* __restrict__ gm7) {
+                                                           char* __restrict__ out, unsigned* __restrict__ gm7,
+                                                           const float* __restrict__ pts) {
   __shared__ __attribute__((aligned(16))) char img[RE_TILES * FB_ENC];
   __shared__ double ebs[64];
   const int t = threadIdx.x;
@@ -3271,7 +3280,7 @@ __global__ __launch_bounds__(32 * RE_TILES) void k_remat_enc(const float* __rest
   float f[64];
   if (i < n) {
     float p[3];
-    sample_point(rays + ray_of(c0 + i, S) * stride, z[c0 + i], p);
+    sample_pos<PT>(rays, stride, z, S, pts, c0 + i, p);
     encode_full(p, f);
   }
   const int sxyz = remat_sx(0, __uint_as_float(*pbound));
@@ -5414,7 +5423,8 @@ static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdW
 // the end for k_wgrad_enc).
 static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
                         const f16x8* pimg, const float* pscl, int64_t ci, int64_t c0, int64_t n, const float* rays,
-                        int ray_stride, const float* z, int n_samples, float eps, const float* grad, hipStream_t s) {
+                        int ray_stride, const float* z, int n_samples, float eps, const float* grad, hipStream_t s,
+                        const float* pts) {
   static std::atomic<uint64_t> attr{0};
   if (pcn_attr_needed(attr)) {
     PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat2<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -5458,8 +5468,13 @@ static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs&
   {
     // the encoding (30 sincosf per sample): 4 B of z in, 256 B of image out per sample
     ProfScope ps(s, PT_BWD_REMAT, 0.0, (4.0 + 256.0) * dn);
-    hipLaunchKernelGGL(k_remat_enc, dim3((unsigned)((ntiles + RE_TILES - 1) / RE_TILES)), dim3(32 * RE_TILES), 0, s,
-                       rays, ray_stride, z, n_samples, c0, n, FB.eb + ci * 64, ws.pbound, encimg, ws.gm7);
+    const dim3 rg((unsigned)((ntiles + RE_TILES - 1) / RE_TILES));
+    if (pts)
+      hipLaunchKernelGGL(k_remat_enc<true>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
+                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
+    else
+      hipLaunchKernelGGL(k_remat_enc<false>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
+                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
   }
   {
     // g_7: 2 x 256 x 64 fp32-FLOP per sample (h_7 - mean_7); 256 B of image + 4 B in, 1 KiB out
@@ -5530,7 +5545,7 @@ static void emit_grads(const GaccLayout& G, const BwdWs& ws, const pcnerf_nof_gr
 static void backward_remat(const float* rays, int ray_stride, const float* z, int n_samples, int64_t total,
                            int64_t chunk, const pcnerf_nof_params* params, float eps, const float* grad,
                            void* workspace, size_t workspace_bytes, const pcnerf_nof_grads* grads, hipStream_t s,
-                           void* fstate, size_t fstate_bytes) {
+                           void* fstate, size_t fstate_bytes, const float* pts = nullptr) {
   PCN_CHECK(g_train_math == 1, "pcnerf_nof_query_train_backward_remat: needs train math 1 (f16x2_3)");
   const BwdWs ws = carve_bwd(workspace, chunk);
   PCN_CHECK(workspace_bytes >= ws.bytes, "pcnerf_nof_query_train_backward_remat: workspace too small");
@@ -5538,21 +5553,22 @@ static void backward_remat(const float* rays, int ray_stride, const float* z, in
   PCN_CHECK(to_dev_params(params, eps, &P), "pcnerf_nof_query_train_backward_remat: null parameter pointer");
   PCN_CHECK(total % chunk != 1 && total != 1, "Expected more than 1 value per channel when training");
   const GaccLayout G = gacc_layout();
-  pos_bound_async(rays, ray_stride, z, n_samples, nullptr, total, ws.pbound, s);
+  pos_bound_async(rays, ray_stride, z, n_samples, nullptr, total, ws.pbound, s, pts);
   hipLaunchKernelGGL(k_wscale, dim3(8), dim3(1024), 0, s, P, ws.sw);
   hipLaunchKernelGGL(k_pack_dgrad_h16, dim3((unsigned)((7 * HW_H + 255) / 256)), dim3(256), 0, s, P, ws.sw,
                      ws.wth16);
   hipLaunchKernelGGL(k_wcol, dim3(7), dim3(256), 0, s, P, ws.wcol);
   PCN_HIP(hipMemsetAsync(ws.gacc, 0, (size_t)G.total * 8, s));
   PCN_HIP(hipMemsetAsync(ws.ostat, 0, sizeof(unsigned), s));   // k_out_gabs's word (k_fb_prep re-zeroes it)
-  const FoldBnBwd FB = fold_bn_backward(rays, ray_stride, z, n_samples, total, chunk, P, grad, fstate, fstate_bytes, s);
+  const FoldBnBwd FB =
+      fold_bn_backward(rays, ray_stride, z, n_samples, total, chunk, P, grad, fstate, fstate_bytes, s, pts);
   // every chunk's P' images at once, into the Sigma products' space (free now)
   f16x8* const pimg = static_cast<f16x8*>(FB.scratch);
   float* const pscl = reinterpret_cast<float*>(pimg + (size_t)8 * FB.C * 256 * 16);
   hipLaunchKernelGGL(k_remat_pimg, dim3(8, (unsigned)FB.C), dim3(256), 0, s, FB, ws.pbound, pimg, pscl);
   for (int64_t c0 = 0; c0 < total; c0 += chunk) {
     const int64_t n = total - c0 < chunk ? total - c0 : chunk;
-    remat_chunk(P, G, ws, FB, pimg, pscl, c0 / chunk, c0, n, rays, ray_stride, z, n_samples, eps, grad, s);
+    remat_chunk(P, G, ws, FB, pimg, pscl, c0 / chunk, c0, n, rays, ray_stride, z, n_samples, eps, grad, s, pts);
   }
   emit_grads(G, ws, grads, s);
   PCN_LAUNCH_CHECK("pcnerf_nof_query_train_backward_remat");
@@ -5786,6 +5802,22 @@ extern "C" int pcnerf_nof_query_train_backward_remat(const float* rays, int64_t 
   const int64_t total = n_rays * (int64_t)n_samples;
   backward_remat(rays, ray_stride, z, n_samples, total, std::min(chunk, total), params, eps, grad_logit, workspace,
                  workspace_bytes, grads, (hipStream_t)stream, state, state_bytes);
+  PCN_API_END
+}
+
+// pcnerf_nof_query_train_backward_remat after pcnerf_nof_points_train_fused_state: the same backward on explicit
+// sample positions
+extern "C" int pcnerf_nof_points_train_backward_remat(const float* pts, int64_t n, int64_t chunk,
+                                                      const pcnerf_nof_params* params, float eps,
+                                                      const float* grad_logit, void* state, size_t state_bytes,
+                                                      void* workspace, size_t workspace_bytes,
+                                                      const pcnerf_nof_grads* grads, void* stream) {
+  PCN_API_BEGIN
+  PCN_CHECK(pts && params && grad_logit && state && workspace && grads,
+            "pcnerf_nof_points_train_backward_remat: null argument");
+  PCN_CHECK(n > 0 && chunk > 0, "pcnerf_nof_points_train_backward_remat: empty input");
+  backward_remat(nullptr, 0, nullptr, 1, n, std::min(chunk, n), params, eps, grad_logit, workspace, workspace_bytes,
+                 grads, (hipStream_t)stream, state, state_bytes, pts);
   PCN_API_END
 }
 

@@ -40,10 +40,11 @@ inline size_t store_layer_bytes(int64_t chunk) {
 }
 constexpr int TQ_COEF_FLOATS = 16 * 256 + 16;   // per chunk: [L][alpha 256 | beta'' 256], then sxB[8] (int)
 void pack_train_query(const NofParamsDev& P, float* img, hipStream_t s);
+// pts != NULL: the explicit-point source ((total, 3) positions; rays, z and ein are not read; no activation store).
 void launch_train_query(const float* rays, int stride, const float* z, int64_t total, int S, const float* ein,
                         const float* img, const float* coef, int64_t chunk, float* p_out, hipStream_t s,
                         float* hst = nullptr, int64_t hst_chunk = 0, int64_t hst_layer = 0,
-                        int64_t store_chunks = 0);
+                        int64_t store_chunks = 0, const float* pts = nullptr);
 
 // The per-sample training backward's BatchNorm statistics from the fused forward's fold state (nof_fold.hip):
 // dg [8][C][256] each BatchNorm's dgamma per chunk, sr [8][C][1024] (s, 1/sqrt(var+eps), mean, var per layer and
@@ -59,7 +60,7 @@ struct FoldBnBwd {
 };
 FoldBnBwd fold_bn_backward(const float* rays, int stride, const float* z, int S, int64_t total, int64_t chunk,
                            const NofParamsDev& P, const float* g_logit, void* state, size_t state_bytes,
-                           hipStream_t s);
+                           hipStream_t s, const float* pts = nullptr);
 
 // p = o + d*z, one rounding per op (render.py:458; built with -ffp-contract=off).
 // ray of flattened sample g (ray-major, S samples per ray): a 32-bit division when g fits (the 64-bit one is a long
@@ -71,6 +72,22 @@ __device__ __forceinline__ void sample_point(const float* __restrict__ r, float 
   p[0] = r[0] + r[3] * z;
   p[1] = r[1] + r[4] * z;
   p[2] = r[2] + r[5] * z;
+}
+// The explicit-point source: sample g's position is pts[3g .. 3g+2], taken verbatim (render.py:18-25 and :44-51
+// embed the caller's materialised samples_xy, whatever produced them).
+__device__ __forceinline__ void load_point(const float* __restrict__ pts, int64_t g, float (&p)[3]) {
+  p[0] = pts[3 * g];
+  p[1] = pts[3 * g + 1];
+  p[2] = pts[3 * g + 2];
+}
+// Position of flattened sample g of a query: the explicit point (PT; rays, stride, z and S are not read), else
+// o + d*z of its ray (pts is not read).  The source is a compile-time choice: every kernel that takes it has one
+// instantiation per source, so the ray form's code does not change with the point form's.
+template <bool PT>
+__device__ __forceinline__ void sample_pos(const float* __restrict__ rays, int stride, const float* __restrict__ z,
+                                           int S, const float* __restrict__ pts, int64_t g, float (&p)[3]) {
+  if constexpr (PT) load_point(pts, g, p);
+  else sample_point(rays + ray_of(g, S) * stride, z[g], p);
 }
 
 // Embedding(3, 10) (models.py:27-41): feature f of [x(3), sin(2^0 x)(3), cos(2^0 x)(3), ..., cos(2^9 x)(3)],

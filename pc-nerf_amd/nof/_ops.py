@@ -412,6 +412,87 @@ def query(model, rays: torch.Tensor, z: torch.Tensor, chunk: int, store=None, fo
     return p
 
 
+def _check_points(pts: torch.Tensor, n_rays: int, n_samples: int) -> None:
+    H.require_device(pts)
+    if pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise RuntimeError("point query: pts must be a contiguous float32 device tensor")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] != int(n_rays) * int(n_samples) or pts.shape[0] == 0:
+        raise RuntimeError(f"point query: pts must be (n_rays * n_samples, 3) = ({int(n_rays) * int(n_samples)}, 3), "
+                           f"got {tuple(pts.shape)}")
+
+
+# samples per piece of the eval fallback's (n, 63) embedding (252 B each: 252 MiB per piece)
+_POINTS_FALLBACK_PIECE = 1 << 20
+
+
+def query_points(model, pts: torch.Tensor, n_rays: int, n_samples: int, chunk: int, keep=None) -> torch.Tensor:
+    """Occupancy p (R, S) of the explicit sample positions ``pts`` (R * S, 3), flattened ray-major, through
+    Embedding + NOF (render.py:18-25 / 44-51 on a caller's samples_xy) -- the positions are taken as given, the
+    encoding is fused into the query.  BatchNorm chunks (train mode) and their bookkeeping are query()'s.
+    ``keep`` (train mode): a fold_state buffer the query keeps its state in for nof_points_backward_remat.
+    Train mode runs under the default train math and backward only (NotImplementedError under the layered maths,
+    the activation-store backward and the train fold); eval mode under set_eval_math("fp32") or set_eval_fold(True)
+    goes through embed + nof_forward_embedded, piecewise (forward-only, not fused)."""
+    L = H.lib()
+    R, S = int(n_rays), int(n_samples)
+    _check_points(pts, R, S)
+    N = R * S
+    st = _stream(pts)
+    if model.training:
+        if _TRAIN_FOLD:
+            raise NotImplementedError("train-mode point queries are not implemented under set_train_fold(True)")
+        if not _TRAIN_FUSED:
+            raise NotImplementedError(f"train-mode point queries are not implemented under "
+                                      f"set_train_math({get_train_math()!r}); use 'f16x2_3_fused'")
+        if _TRAIN_BACKWARD != "remat":
+            raise NotImplementedError("train-mode point queries are not implemented under "
+                                      "set_train_backward('store'); use 'remat'")
+        p = torch.empty((R, S), dtype=torch.float32, device=pts.device)
+        chunk = max(1, min(int(chunk), N))
+        mom, eps = _bn_config(model)
+        s, keep_params = _params(model)
+        _bn_before(model)
+        if keep is not None:
+            H.check(L.pcnerf_nof_points_train_fused_state(pts.data_ptr(), N, chunk, ctypes.byref(s), mom, eps,
+                                                          keep.data_ptr(), keep.numel(), p.data_ptr(), st))
+            _bn_after(model, keep, N, chunk)
+        else:
+            ws = _workspace(pts.device, int(L.pcnerf_nof_train_fused_bytes(N, chunk)))
+            H.check(L.pcnerf_nof_points_train_fused(pts.data_ptr(), N, chunk, ctypes.byref(s), mom, eps,
+                                                    ws.data_ptr(), ws.numel(), p.data_ptr(), st))
+            _bn_after(model, ws, N, chunk)
+        _track_batches(model, -(-N // chunk))
+        return p
+    if _EVAL_FOLD or get_eval_math() != "f16x2_3":
+        out = [nof_forward_embedded(model, embed(pts[i:i + _POINTS_FALLBACK_PIECE]))
+               for i in range(0, N, _POINTS_FALLBACK_PIECE)]
+        return (out[0] if len(out) == 1 else torch.cat(out, dim=0)).reshape(R, S)
+    p = torch.empty((R, S), dtype=torch.float32, device=pts.device)
+    packed = pack_eval(model, pts.device)
+    H.check(L.pcnerf_nof_points_eval(pts.data_ptr(), N, packed.data_ptr(), p.data_ptr(), st))
+    return p
+
+
+def nof_points_backward_remat(model, pts: torch.Tensor, chunk: int, g_logit, state) -> list:
+    """Parameter gradients (grad_params order) of the train-mode point query whose forward kept ``state``
+    (query_points(..., keep=state)); the state is consumed."""
+    L = H.lib()
+    N = pts.shape[0]
+    _check_points(pts, N, 1)
+    chunk = max(1, min(int(chunk), N))
+    _, eps = _bn_config(model)
+    s, keep = _params(model)
+    gs, out = _grads_struct(model, pts.device)
+    ws = _workspace(pts.device, L.pcnerf_nof_backward_workspace_bytes(int(chunk)))
+    g = _f32(g_logit)
+    if g.numel() != N:
+        raise RuntimeError("point query backward: one logit gradient per sample expected")
+    H.check(L.pcnerf_nof_points_train_backward_remat(pts.data_ptr(), N, chunk, ctypes.byref(s), eps, g.data_ptr(),
+                                                     state.data_ptr(), state.numel(), ws.data_ptr(), ws.numel(),
+                                                     ctypes.byref(gs), _stream(pts)))
+    return out
+
+
 def nof_forward_embedded(model, x: torch.Tensor, with_fold_state: bool = False):
     """NOF.forward on a (B, 63) embedded batch (one BatchNorm batch in train mode).  ``with_fold_state``: return
     (p, fold state or None) -- the state the train fold's backward needs when set_train_fold(True)."""

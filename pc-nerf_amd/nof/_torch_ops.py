@@ -192,6 +192,37 @@ def _(rays, z, packed):
     return torch.empty_like(z)
 
 
+def _check_points_query(pts: Tensor, packed: Tensor) -> None:
+    """The host-side checks before pcnerf_nof_points_eval's launch: its grid and reads assume these layouts."""
+    H.require_device(pts, packed)
+    for name, t in (("pts", pts), ("packed", packed)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"pcnerf::query_points_eval: {name} must be a contiguous float32 device tensor")
+    if pts.dim() not in (2, 3) or pts.shape[-1] != 3 or pts.numel() == 0:
+        raise RuntimeError(f"pcnerf::query_points_eval: pts (N, 3) or (R, S, 3) expected, got {tuple(pts.shape)}")
+    if packed.numel() != _packed_floats():
+        raise RuntimeError(f"pcnerf::query_points_eval: packed must be pcnerf::pack_eval's image ({_packed_floats()} "
+                           f"floats), got {packed.numel()}")
+    if pts.device != packed.device:
+        raise RuntimeError("pcnerf::query_points_eval: pts and packed must be on one device")
+
+
+@torch.library.custom_op(f"{NS}::query_points_eval", mutates_args=())
+def query_points_eval(pts: Tensor, packed: Tensor) -> Tensor:
+    """Eval-mode occupancy of explicit sample positions through Embedding + NOF (render.py:18-25 on a caller's
+    samples_xy, models.py:183-203): pts (N, 3) -> (N,), pts (R, S, 3) -> (R, S).  The positions are taken as given."""
+    _check_points_query(pts, packed)
+    p = torch.empty(tuple(pts.shape[:-1]), dtype=torch.float32, device=pts.device)
+    H.check(H.lib().pcnerf_nof_points_eval(pts.data_ptr(), p.numel(), packed.data_ptr(), p.data_ptr(),
+                                           H.stream_of(pts)))
+    return p
+
+
+@query_points_eval.register_fake
+def _(pts, packed):
+    return pts.new_empty(tuple(pts.shape[:-1]), dtype=torch.float32)
+
+
 # ----------------------------------------------------------------------------------------------- compositing
 @torch.library.custom_op(f"{NS}::composite", mutates_args=())
 def composite(p: Tensor, z: Tensor, noise: Optional[Tensor], noise_std: float, eps: float, rays: Optional[Tensor],
@@ -317,6 +348,6 @@ pointwise_loss.register_autograd(_pl_backward, setup_context=_pl_setup)
 
 def op_names() -> list:
     """The registered operator names (tests)."""
-    return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "composite",
+    return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "query_points_eval", "composite",
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
             "pointwise_loss_backward"]

@@ -9,6 +9,8 @@ lib/libpcnerf_hip.so (see include/pcnerf_hip.h):
     compositing, child masks, loss terms  pcnerf_composite          render.py:51-61, 75-159
     sample_pdf + sort(cat(z, samples))    pcnerf_resample           render.py:371-412, 463-467
     child loss reductions                 pcnerf_child_loss_reduce  render.py:102-159
+    query of materialised samples_xy      pcnerf_nof_points_*       render.py:13-25, 38-51, 166-201, 229-241
+      (inference_val / inference_train / inference / inference_0525_2: the positions are read verbatim)
 
 Differences from the reference, all deliberate:
   * everything stays on ``rays.device`` (the reference pins ``u`` to ``cuda:0``, render.py:397);
@@ -110,6 +112,145 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False, *, u=None):
         u = torch.from_numpy(np.ascontiguousarray(hu, dtype=np.float32)).to(bins.device)
         det = False   # the uploaded draws are used as given (the linspace is numpy's, float64 rounded to float32)
     return P.sample_pdf(bins, weights, int(N_samples), bool(det), u)
+
+
+# ----------------------------------------------------------------------------------------------- inference_*
+# The reference's module-level helpers (render.py:13, :38, :166, :229): they take MATERIALISED sample positions
+# samples_xy (R, S, 3) and a separate z_vals (R, S); the positions need not lie on any ray.  The query reads them
+# verbatim through the point-sourced fused kernels (pcnerf_nof_points_*), everything after it is the renderers'
+# kernels on a small per-ray table built on the device.
+def _query_points(model, pts, R, S, chunk):
+    """_query on explicit positions: eval mode through pcnerf::query_points_eval, train mode and the opt-in eval
+    paths (fold, fp32 math: embed + embedded forward) through nof._ops.query_points."""
+    if not model.training and not _ops.eval_fold_enabled() and _ops.get_eval_math() == "f16x2_3":
+        _ops._bn_config(model)
+        return P.query_points_eval(pts.view(R, S, 3), P.pack_eval(_torch_ops.eval_params(model)))
+    return _ops.query_points(model, pts, R, S, chunk)
+
+
+def _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child=None, differentiable=False):
+    """_check_inputs for the inference_* helpers -> (pts (R * S, 3), z (R, S)) contiguous float32."""
+    for name, t in (("samples_xy", samples_xy), ("z_vals", z_vals), ("near_far_child", near_far_child)):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError(f"nof.render (HIP) takes device-resident tensors; move {name} with .to('cuda') -- "
+                               "there is no CPU path")
+    if samples_xy.dim() != 3 or samples_xy.shape[2] != 3 or samples_xy.numel() == 0:
+        raise RuntimeError(f"samples_xy must be (N_rays, N_samples, 3); got {tuple(samples_xy.shape)}")
+    R, S = samples_xy.shape[:2]
+    if tuple(z_vals.shape) != (R, S):
+        raise RuntimeError(f"z_vals must be (N_rays, N_samples) = ({R}, {S}); got {tuple(z_vals.shape)}")
+    if near_far_child is not None and tuple(near_far_child.shape) != (R, 2):
+        raise RuntimeError(f"near_far_child must be (N_rays, 2) = ({R}, 2); got {tuple(near_far_child.shape)}")
+    if embedding_xy is not None and not embedding_xy.supported():
+        raise NotImplementedError("HIP render supports Embedding(3, 10) (L_pos = 10)")
+    if not model.supported():
+        raise NotImplementedError("HIP render supports NOF(feature_size=256, in_channels_xy=63, use_skip=True)")
+    if _autograd.needs_grad(model):
+        if not differentiable:
+            raise NotImplementedError("this HIP inference helper is forward-only; call it under torch.no_grad()")
+        _autograd.check_trainable(model)
+    if samples_xy.requires_grad:
+        raise NotImplementedError("no gradient flows to samples_xy through the HIP query; detach it")
+    return samples_xy.detach().float().contiguous().view(-1, 3), z_vals.detach().float().contiguous()
+
+
+def inference_val(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tensor, rays: torch.Tensor,
+                  z_vals: torch.Tensor, near_far_child: torch.Tensor, near_far_point: torch.Tensor,
+                  range_readings: torch.Tensor, ray_class: torch.Tensor, chunk=1024 * 32, noise_std=1, epsilon=1e-10,
+                  isval=False, sub_nerf_test_num=4, *, rng=None):
+    """render.py:13-36 -> (depth_final (R,), weights_origin (R, S)).  ``rays``, ``near_far_point``,
+    ``range_readings``, ``ray_class``, ``isval`` and ``sub_nerf_test_num`` are accepted and unused, as in the
+    reference.  ``rng["noise"]`` (R, S) injects the randn draw (taken only when noise_std != 0)."""
+    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child)
+    p = _query_points(model, pts, z.shape[0], z.shape[1], chunk)
+    w, depth, _, _ = P.composite(p, z, _noise(rng, "noise", z, noise_std), float(noise_std), float(epsilon), None,
+                                 10, 11, 14, True)
+    return depth, w
+
+
+def _child_table(rays, near_far_child, range_readings, R, divide):
+    """The (R, 15) per-ray table the compositing / child-loss kernels read by column: child id (rays[:, 9], divide
+    branch only) in column 9, near_far_child in 10:12, range_readings in 14."""
+    table = torch.zeros((R, 15), dtype=torch.float32, device=near_far_child.device)
+    table[:, 10:12] = near_far_child
+    if not (torch.is_tensor(range_readings) and range_readings.is_cuda):
+        raise RuntimeError("nof.render (HIP) takes device-resident tensors; move range_readings with .to('cuda')")
+    if range_readings.numel() != R:
+        raise RuntimeError(f"range_readings must have one entry per ray ({R}); got {tuple(range_readings.shape)}")
+    table[:, 14] = range_readings.reshape(-1)
+    if divide:
+        if not (torch.is_tensor(rays) and rays.is_cuda):
+            raise RuntimeError("nof.render (HIP) takes device-resident tensors; move rays with .to('cuda')")
+        if rays.dim() != 2 or rays.shape[0] != R or rays.shape[1] < 10:
+            raise RuntimeError(f"rays must be (N_rays, >=10) = ({R}, >=10); got {tuple(rays.shape)}")
+        table[:, 9] = rays[:, 9]
+    return table
+
+
+def inference_train(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tensor, rays: torch.Tensor,
+                    z_vals: torch.Tensor, near_far_child: torch.Tensor, near_far_point: torch.Tensor,
+                    range_readings: torch.Tensor, ray_class: torch.Tensor, chunk=1024 * 32, noise_std=1,
+                    epsilon=1e-10, isval=False, sub_nerf_test_num=4, use_child_nerf_divide=1, use_child_nerf_loss=0,
+                    *, rng=None):
+    """render.py:38-163 -> (child_free_loss, child_depth_loss, depth_final (R,), weights_origin (R, S)).  The losses
+    are CPU ``torch.tensor(0.0)`` when use_child_nerf_loss != 1 and have shape (1,) in the divide branch.
+    Differentiable under autograd with a train-mode module (the conditions of render_rays_train); no gradient flows
+    to samples_xy.  ``near_far_point``, ``ray_class`` and ``isval`` are accepted and unused."""
+    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child, differentiable=True)
+    R, S = z.shape
+    with_losses = use_child_nerf_loss == 1
+    divide = use_child_nerf_divide == 1
+    table = _child_table(rays, near_far_child, range_readings, R, divide) if with_losses else None
+    noise = _noise(rng, "noise", z, noise_std)
+    if _autograd.needs_grad(model):
+        sub = int(sub_nerf_test_num) if divide else 0
+        w, depth, free, dl = _autograd.TrainPassPoints.apply(model, pts, table, z, noise, float(noise_std),
+                                                             float(epsilon), int(chunk), with_losses, sub,
+                                                             *_ops.grad_params(model))
+    else:
+        p = _query_points(model, pts, R, S, chunk)
+        w, depth, fr, sl = P.composite(p, z, noise, float(noise_std), float(epsilon), table, 10, 11, 14, True)
+        if with_losses:
+            free, dl = P.child_losses(fr, sl, table, divide, int(sub_nerf_test_num))
+    if not with_losses:
+        free, dl = torch.tensor(0.0), torch.tensor(0.0)   # render.py:123-125, 157-159 (CPU scalars)
+    return free, dl, depth, w
+
+
+def inference(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tensor, z_vals: torch.Tensor,
+              chunk=1024 * 32, noise_std=1, epsilon=1e-10, isval=False, *, rng=None):
+    """render.py:166-226 -> (depth_final (R,), weights (R, S), opacity ()).  ``isval=True`` (un-normalised weights,
+    render.py:219) is reached by no reference caller -- render_rays passes its isval into the ``epsilon`` slot -- and
+    raises NotImplementedError here."""
+    if not (isval == False):   # noqa: E712  (the reference's own test, render.py:219)
+        raise NotImplementedError("inference(isval=True) (un-normalised weights) is not implemented: no reference "
+                                  "caller reaches it (render_rays passes isval as epsilon)")
+    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals)
+    p = _query_points(model, pts, z.shape[0], z.shape[1], chunk)
+    w, depth, opac, _ = P.composite_extras(p, z, _noise(rng, "noise", z, noise_std), float(noise_std),
+                                           float(epsilon))
+    return depth, w, opac
+
+
+def inference_0525_2(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tensor, z_vals: torch.Tensor,
+                     other_interest_sub_nerf_number: torch.Tensor, near_far_child: torch.Tensor, chunk=1024 * 32,
+                     noise_std=1, epsilon=0, isval=False, is_fine=0, depth_inference_method=0, *, rng=None):
+    """render.py:229-368 -> (depth_final (R,), weights (R, S), opacity (), rays_effective_flag (R, 1) bool).  Adds
+    no noise (the reference does not) and never prints; ``noise_std``, ``isval`` and ``is_fine`` are accepted and
+    unused."""
+    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child)
+    R, S = z.shape
+    other = other_interest_sub_nerf_number
+    if not torch.is_tensor(other):
+        other = torch.as_tensor(other)
+    other = other.to(z.device)
+    p = _query_points(model, pts, R, S, chunk)
+    rows = torch.zeros((R, 8), dtype=torch.float32, device=z.device)   # view_rows reads the child bounds in 6:8
+    rows[:, 6:8] = near_far_child
+    w, depth, at_peak, csum, opac_row, _ = _ops.view_rows(p, z, rows, int(depth_inference_method), float(epsilon),
+                                                          want_points=False)
+    flags, opacity = P.view_walk(other, at_peak, csum, opac_row, int(S))
+    return depth, w, opacity, flags
 
 
 def render_rays_train(model: NOF, model_fine: NOF, embedding_xy: Embedding, rays: torch.Tensor, sub_nerf_test_num=4,
