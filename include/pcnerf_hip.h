@@ -65,6 +65,13 @@ int pcnerf_set_eval_math(int mode);
  * the same bits; the setting exists for A/B timing and the bit-identity tests. */
 int pcnerf_set_query_geometry(int geometry);
 
+/* Form of the store-less train-mode query where it runs as the 8-wave workgroup with the 2-slot ring (query geometry
+ * -1 or 1), process-wide; returns the previous setting, or -2 for an invalid one.  -1 (default): the measured
+ * default (form 2).  0: 6 sample blocks, 96 samples per pass over the weight image.  2: 7 sample blocks, 112 samples
+ * per pass.  (1 was a half-skewed schedule of form 0; it measured slower and is not built: refused.)  Every form
+ * computes the same bits; for A/B timing and the bit-identity tests. */
+int pcnerf_set_train_query_form(int form);
+
 /* Fused eval-mode query: for every flattened sample g = ray*n_samples + s computes
  *   p_out[g] = NOF(Embedding(o + d*z[g]))        (render.py:18-25 chunk loop, models.py:27-41, :183-203)
  * with o = rays[ray, 0:3], d = rays[ray, 3:6]. */

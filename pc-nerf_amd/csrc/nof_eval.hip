@@ -255,10 +255,11 @@ __device__ __forceinline__ void eh_split8(const float (&v)[8], eh_f16x8& hi, eh_
 // accumulation), fused over all 9 layers for a block of 16 SB samples with the work split over NEURONS: wave w of NW
 // owns J = 16 / NW neuron blocks (neurons 16 J w .. 16 J (w + 1) - 1) of every layer for all the block's samples, so
 // each wave streams only its own neurons' weights from L2 (an R3-slot register ring, R3 - 1 k-steps of prefetch, no
-// barrier) and each A operand feeds SB sample blocks.  Two geometries, the same 96 samples and two waves per SIMD on
-// a CU either way: <NW 4, SB 3> (two workgroups of 48 samples per CU, each streaming the whole image: the eval query
-// and the store-writing train query) and <NW 8, SB 6> (one workgroup, one pass over the image: the train query);
-// every accumulator sees the same products in the same order in both (the formulas below are for NW = 4: J = 4);
+// barrier) and each A operand feeds SB sample blocks.  Two geometries, two waves per SIMD on a CU either way:
+// <NW 4, SB 3> (two workgroups of 48 samples per CU, each streaming the whole image: the eval query and the
+// store-writing train query) and <NW 8, SB 6 or 7> (one workgroup of 96 or 112 samples, one pass over the image: the
+// store-less train query, 7 blocks by default -- EH3_TRAIN_FORM below);
+// every accumulator sees the same products in the same order in all of them (the formulas below are for NW = 4: J = 4);
 // the layer outputs go through LDS as the next layer's split B operands ([k-step][sample block][part][lane],
 // 16 KiB per sample block), two barriers per layer.  The encoding lives in LDS as layer 0's split B operands; layer 4 re-splits it
 // (hi + mid is exact in fp32) at the per-sample scale it shares with h3.
@@ -316,13 +317,15 @@ __global__ void k_pack_eval_h3(NofParamsDev P, float* __restrict__ out) {
 // (barriers, epilogue, split) and prologue run under the other's MFMAs: against one workgroup of 6 blocks per CU,
 // store-writing train query 87.5 -> 78.6 ms and eval query 64.0 -> 61.7 ms at 25.2M samples, bit-identical; MfmaUtil
 // 38.9 -> 55.3 % / 49.4 -> 61.7 % (profiles/r04_occupancy_*.json; the clock drops ~20 %: the board's power limit).
-// One workgroup per CU: 5, 7 or 3 blocks all slower than 6 (profiles/r03l_variants_eval_sb*.json, r04_occupancy_ab).
+// One 4-wave workgroup per CU: 5, 7 or 3 blocks all slower than 6 (profiles/r03l_variants_eval_sb*.json,
+// r04_occupancy_ab); in the 8-wave form of the train query 7 blocks are faster than 6 (profiles/TRAIN_QUERY_FORM.md).
 constexpr int EH3_SB = 3;
 constexpr int EH3_WG_PER_CU = 2;
 static_assert(96 % (16 * EH3_SB) == 0, "store_layer_bytes (pcnerf_internal.h) pads a chunk to whole 96-sample blocks");
 // The wide geometry <NW = 8, SB = 6>: the same 96 samples per CU as ONE workgroup of 8 waves, wave w owning neuron
 // blocks 2w, 2w + 1 (J = 2), so a CU streams the weight image once per 96 samples instead of twice; still two waves
 // per SIMD, but the two halves no longer run independent phases.  ~140 KiB of LDS, __launch_bounds__(512, 1).
+// (The store-less train query runs it with 7 blocks, 112 samples, by default: EH3_SB_WIDE7 below.)
 constexpr int EH3_SB_WIDE = 6;
 static_assert(96 % (16 * EH3_SB_WIDE) == 0, "store_layer_bytes pads a chunk to whole 96-sample blocks");
 // k_nof_eval_h3: weight-ring slots (prefetch distance R3 - 1 k-steps of 32).  The ring index is pos % R3 with pos a
@@ -820,12 +823,29 @@ static int g_query_geometry = -1;
 // takes the 8-wave form (config 2 forward 83.31 -> 80.02 ms, L2 read requests halved, clock up), the eval query stays
 // on the 4-wave form (8 waves: +0.3 %, inside the spread); the 4-slot ring lost in both geometries and both queries.
 constexpr int EH3_GEOM_EVAL = 0, EH3_GEOM_TRAIN = 1;
+// Form of the store-less train query where it runs in the 8-wave geometry with the 2-slot ring (geometry -1 or 1;
+// pcnerf_set_train_query_form): 0 = 6 sample blocks (96 samples per pass over the weight image), 2 = 7 sample blocks
+// (112 samples per pass: 6/7 of the L2 weight stream per sample; 163,328 B of LDS -- the train form without the store
+// allocates no smax / emax / sbraw, so it just fits the CU's 160 KiB; 213 VGPRs); -1 = the measured default, form 2
+// (config 2 forward 77.63 -> 76.21 ms, profiles/TRAIN_QUERY_FORM.md).  1 was the half-skewed form: measured slower,
+// not built (HISTORY.md).  Same bits in every form (tests/test_train_query_form_gpu.py).
+static int g_train_query_form = -1;
+constexpr int EH3_TRAIN_FORM = 2;
+constexpr int EH3_SB_WIDE7 = 7;
 
 // launches k_nof_eval_h3<TR, false> in geometry geom: `rows` grid rows (BatchNorm chunks) of `span` samples each
 // (PT: the point source, the positions in the kernel's `rays` argument)
 template <bool TR, bool PT, typename... Args>
 static void launch_h3(int geom, int64_t span, unsigned rows, hipStream_t s, Args... args) {
   const bool wide = geom & 1, deep = geom & 2;
+  if constexpr (TR) {   // the 7-block form of the 8-wave train query (pcnerf_set_train_query_form)
+    if (wide && !deep && (g_train_query_form < 0 ? EH3_TRAIN_FORM : g_train_query_form) == 2) {
+      const int64_t ns7 = 16 * EH3_SB_WIDE7;
+      hipLaunchKernelGGL((k_nof_eval_h3<true, false, 8, EH3_SB_WIDE7, EH3_RING, PT>),
+                         dim3((unsigned)((span + ns7 - 1) / ns7), rows), dim3(512), 0, s, args...);
+      return;
+    }
+  }
   const int64_t ns = 16 * (wide ? EH3_SB_WIDE : EH3_SB);
   const dim3 grid((unsigned)((span + ns - 1) / ns), rows), block(wide ? 512 : 256);
   if (wide && deep)
@@ -1178,6 +1198,17 @@ extern "C" int pcnerf_set_query_geometry(int geometry) {
   }
   const int prev = pcn::g_query_geometry;
   pcn::g_query_geometry = geometry;
+  return prev;
+}
+
+extern "C" int pcnerf_set_train_query_form(int form) {
+  if (form != -1 && form != 0 && form != 2) {
+    pcn::set_error("pcnerf_set_train_query_form: train_query_form must be -1 (default), 0 (6 sample blocks) or 2 "
+                   "(7 sample blocks); 1 (half-skewed) is not built");
+    return -2;
+  }
+  const int prev = pcn::g_train_query_form;
+  pcn::g_train_query_form = form;
   return prev;
 }
 

@@ -47,6 +47,7 @@ _SIGS = {
     "pcnerf_set_composite_group": (c_int, [c_int]),
     "pcnerf_set_eval_math": (c_int, [c_int]),
     "pcnerf_set_query_geometry": (c_int, [c_int]),
+    "pcnerf_set_train_query_form": (c_int, [c_int]),
     "pcnerf_nof_query_train": (c_int, [vp, i64, c_int, vp, c_int, i64, ctypes.POINTER(NofParams), c_float, c_float,
                                        vp, c_size, vp, vp]),
     "pcnerf_sample_coarse": (c_int, [vp, i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp]),

@@ -208,6 +208,20 @@ if os.environ.get("PCNERF_QUERY_GEOMETRY"):
     set_query_geometry(int(os.environ["PCNERF_QUERY_GEOMETRY"]))
 
 
+def set_train_query_form(form: int) -> int:
+    """Form of the store-less train query in its 8-wave geometry (pcnerf_set_train_query_form): -1 the default
+    (form 2), 0 = 6 sample blocks (96 samples per workgroup), 2 = 7 sample blocks (112); 1 (half-skewed) is not
+    built.  Same bits in every form; for A/B timing and tests.  Returns the previous setting."""
+    prev = H.lib().pcnerf_set_train_query_form(int(form))
+    if prev < -1:
+        raise ValueError(H.lib().pcnerf_last_error().decode())
+    return prev
+
+
+if os.environ.get("PCNERF_TRAIN_QUERY_FORM"):
+    set_train_query_form(int(os.environ["PCNERF_TRAIN_QUERY_FORM"]))
+
+
 # render_rays' depth2 (render.py:598-600) ranks the last sample in argsort(weights, descending=True); where weights
 # tie exactly (every weight after an opaque sample is 0) the order of equal keys decides.  "stable" (default): the
 # order torch's sort gives on the GPU, where the reference runs render_rays (it moves the draws to cuda:0,
