@@ -40,17 +40,6 @@ constexpr int H1_XD = H_XD;      // k_train_h1's B-operand read ring depth
 // blocks later), the block of the first staging piece, the blocks between staging pieces
 constexpr int WB3_AREAD = 3, WB3_STAGE = 0, WB3_SPACE = 2;
 
-#ifndef PCN_RB_CLK
-#define PCN_RB_CLK 0   // diagnostic builds: per-wave shader cycles of the layer-2 launch's phases (pcnerf_debug_rbclk)
-#endif
-#if PCN_RB_CLK
-// [block * 8 + wave]: cycles summed over the tiles of: phase A (D: data-gradient MFMAs; W: remat), phase B (D:
-// epilogue; W: weight-gradient MFMAs), the end-of-tile wait + barrier; the loop; the tile count
-__device__ unsigned long long g_rbclk[4096][5];
-#define RB_T(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define RB_T(v) do { } while (0)
-#endif
 #ifndef PCN_CLOCK_STAMP
 #define PCN_CLOCK_STAMP 0  // diagnostic builds only: phase stamps of 1 k_train_ws, 2 k_wgrad (pcnerf_debug_clock)
 #endif
@@ -1361,30 +1350,11 @@ struct TrainWs {
 // products (k_train_h).  Process-wide; pcnerf_set_train_math.  Mode 1 renders config 2 within 1.9e-5 of a float64
 // evaluation of the same rays (fp32 MFMA: 2.2e-5; the reference itself: 1.1e-4) at 1.9x the speed.
 static int g_train_math = 1;
-// The rematerialised backward's layer kernel: 4 = k_bwd_remat3<true> (default: weight gradient over the encoding
-// columns, projected by P'^T per chunk; BatchNorm-backward epilogue on the W waves), 3 = k_bwd_remat3<false> (the
-// epilogue on the D waves), 2 = k_bwd_remat2 (round 5's: over the rematerialised x columns).  PCNERF_REMAT_VER
-// selects it at load time (A/B measurements).
-static int remat_ver_env() {
-  const char* v = getenv("PCNERF_REMAT_VER");
-  return (v && v[0] == '2') ? 2 : (v && v[0] == '3') ? 3 : 4;
-}
-static int g_remat_ver = remat_ver_env();
-// version 4's layer-1 launch forms dW_0's encoding columns itself (k_bwd_remat3<true, true>; default); 0 keeps
-// k_wgrad_enc on the stored g_0 (PCNERF_REMAT_FUSE0=0 / pcnerf_set_remat_fuse0, A/B)
-// version 4's hidden layers with eight W waves (three waves per SIMD: each W wave half the epilogue / remat / G_d
-// rows); PCNERF_REMAT_W8=1 (A/B)
-#ifndef PCN_R3_W8_DEFAULT
-#define PCN_R3_W8_DEFAULT 0
-#endif
-static int g_remat_w8 = [] {
-  const char* v = getenv("PCNERF_REMAT_W8");
-  return v ? (v[0] == '1' ? 1 : 0) : PCN_R3_W8_DEFAULT;
-}();
-static int g_remat_fuse0 = [] {
-  const char* v = getenv("PCNERF_REMAT_FUSE0");
-  return (v && v[0] == '0') ? 0 : 1;
-}();
+// The rematerialised backward's layer kernel (pcnerf_set_remat_version): 4 = k_bwd_remat3 (default: weight gradient
+// over the encoding columns, projected by P'^T per chunk; BatchNorm-backward epilogue on the W waves; layer 1's launch
+// forms dW_0's encoding columns itself), 2 = k_bwd_remat2 (round 5's: over the rematerialised x columns; kept for
+// A/B).  3 was k_bwd_remat3 with the epilogue on the D waves: measured slower, not built (HISTORY.md).
+static int g_remat_ver = 4;
 
 static TrainWs carve(void* base, int64_t chunk) {
   const size_t tiles = (size_t)((chunk + 31) / 32);
@@ -1431,9 +1401,9 @@ extern "C" int pcnerf_set_train_math(int mode) {
 }
 
 extern "C" int pcnerf_set_remat_version(int version) {
-  if (version < 2 || version > 4) {
-    pcn::set_error("pcnerf_set_remat_version: version must be 2 (k_bwd_remat2), 3 (k_bwd_remat3) or 4 "
-                   "(k_bwd_remat3 with the epilogue on the W waves)");
+  if (version != 2 && version != 4) {
+    pcn::set_error("pcnerf_set_remat_version: remat_version must be 4 (k_bwd_remat3) or 2 (k_bwd_remat2); 3 "
+                   "(k_bwd_remat3 with the epilogue on the D waves) is no longer built");
     return -1;
   }
   const int prev = pcn::g_remat_ver;
@@ -1488,12 +1458,6 @@ static void pack_weights(const NofParamsDev& P, float* wp, f16x8* wh, int* sw, h
   }
 }
 }  // namespace pcn
-
-#if PCN_RB_CLK
-extern "C" int pcnerf_debug_rbclk(unsigned long long* out) {   // out: [4096][5] (g_rbclk)
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(pcn::g_rbclk), sizeof(pcn::g_rbclk)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 #if PCN_CLOCK_STAMP
 // diagnostic builds: median over workgroups of the last hidden-layer launch's in-kernel clock (MHz) and cycles
@@ -3787,7 +3751,7 @@ __global__ __launch_bounds__(512, 1) void k_g7(const char* __restrict__ enc, con
         }
         s16x4 p0, p1;
         split2_x4(v, p0, p1);
-        // one 16-byte cell per lane, as k_bwd_remat2's epilogue: kg even / odd (features f .. f+3, f+4 .. f+7 of
+        // one 16-byte cell per lane, as k_bwd_remat3's epilogue: kg even / odd (features f .. f+3, f+4 .. f+7 of
         // one octet) swap halves, the even row storing the octet's hi part and the odd row its mid part
         const fb_i32x2 hv = __builtin_bit_cast(fb_i32x2, p0), mv = __builtin_bit_cast(fb_i32x2, p1);
         const auto s0 = __builtin_amdgcn_permlane16_swap(hv[0], mv[0], false, false);
@@ -4007,12 +3971,9 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
     // stores do not meet every CU's at the epilogue: -1.6 % per launch (profiles/r05_variants_remat2_defer.txt)
     // (tile 0: zero cells to tile 0's own slots, rewritten by this wave's later stores of its real cells -- same
     // addresses, program order; they also keep NST stores behind every tile's DMAs for the vmcnt(NST) below)
-    [[maybe_unused]] unsigned long long ck0 = 0, ck1 = 0, ck2 = 0, ck3 = 0, cA = 0, cB = 0, cW = 0, cL0 = 0, cL1 = 0;
-    RB_T(cL0);
     for (int k = 0; k < nk; ++k) {
       const int tl = pr + k * npair;
       const int ptl = k > 0 ? tl - npair : tl;
-      RB_T(ck0);
 #if !PCN_RB_NODMA
       if (k + 1 < nk) dma_g(k + 1);
       if (k + 2 < nk) dma_enc(k + 2);
@@ -4042,7 +4003,6 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-      RB_T(ck1);
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
         const int il = 32 * rw + 16 * rb + 4 * kg;
@@ -4074,24 +4034,12 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
           pcell[rb][sb] = u32x4{s0[0], s1[0], s0[1], s1[1]};
         }
       }
-      RB_T(ck2);
 #if !PCN_RB_NOWAIT
       __builtin_amdgcn_s_waitcnt(fb_vmcnt(NST));   // this wave's DMAs (its stores may fly)
 #endif
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_s_barrier();
-      RB_T(ck3);
-      cA += ck1 - ck0;
-      cB += ck2 - ck1;
-      cW += ck3 - ck2;
     }
-    RB_T(cL1);
-#if PCN_RB_CLK
-    if (layer == 2 && lane == 0 && bid < 512) {
-      unsigned long long* g = g_rbclk[bid * 8 + wv];
-      g[0] = cA; g[1] = cB; g[2] = cW; g[3] = cL1 - cL0; g[4] = (unsigned long long)nk;
-    }
-#endif
     if (nk > 0) {   // the last tile's cells
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
@@ -4108,10 +4056,7 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
 #pragma unroll
       for (int ib = 0; ib < 8; ++ib) aw[jb][ib] = f32x4{};
     const int trq = lm >> 2, trp = lm & 3;
-    [[maybe_unused]] unsigned long long ck0 = 0, ck1 = 0, ck2 = 0, ck3 = 0, cA = 0, cB = 0, cW = 0, cL0 = 0, cL1 = 0;
-    RB_T(cL0);
     for (int k = 0; k < nk; ++k) {
-      RB_T(ck0);
 #if !PCN_RB_NODMA
       if (k + 1 < nk) dma_g(k + 1);
       if (k + 2 < nk) dma_enc(k + 2);
@@ -4119,7 +4064,6 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
 #if !PCN_RB_NORM
       if (k + 1 < nk) remat_x(k + 1);
 #endif
-      RB_T(ck1);
       const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
       auto read8 = [&](unsigned a0, unsigned a1, auto partc) {
         constexpr int Q = decltype(partc)::value;
@@ -4173,24 +4117,12 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
 #endif
         }
       }
-      RB_T(ck2);
 #if !PCN_RB_NOWAIT
       __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
 #endif
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_s_barrier();
-      RB_T(ck3);
-      cA += ck1 - ck0;
-      cB += ck2 - ck1;
-      cW += ck3 - ck2;
     }
-    RB_T(cL1);
-#if PCN_RB_CLK
-    if (layer == 2 && lane == 0 && bid < 512) {
-      unsigned long long* g = g_rbclk[bid * 8 + wv];
-      g[0] = cA; g[1] = cB; g[2] = cW; g[3] = cL1 - cL0; g[4] = (unsigned long long)nk;
-    }
-#endif
     float* pb = part + (size_t)pr * WgradCfg<LAY>::PART;
 #pragma unroll
     for (int ib = 0; ib < 8; ++ib) {
@@ -4219,16 +4151,15 @@ __global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ 
 //   G_L = sum_s g_L (x) x = (sum_s g_L (x) d) P'_{L-1}^T :
 // the tile loop contracts g_L with the 64 encoding columns (24 MFMAs per W wave and tile instead of 96 over the 256
 // x columns) and k_gd_proj applies P'_{L-1}^T in float64 once per chunk and layer (256 x 64 x 256).  x itself is
-// still made per tile (the BatchNorm backward's x kk term), but only as that term: the W waves write
-// xc = x (kk invstd gamma 2^eo) + gm invstd gamma 2^eo in fp32 (no hi / mid split: x is no longer an MFMA operand),
-// and the D waves' epilogue is one fma, 2^eo g_{L-1} = dy A - xc.  Per SIMD and tile the matrix pipe carries 96 + 24
-// + 24 MFMA groups instead of 96 + 24 + 96.  The weight-gradient partials (per pair: 256 rows x the half's 32 encoding
-// columns, in k_wgrad_enc's 64-column layout) are 4x smaller; the next launch's tail sums them per row into the
-// chunk's float64 G_d (gd_reduce_row), k_gd_tail sums layer 1's.  The skip layer's encoding columns ARE its G_d, so
-// k_wgrad_enc is left with g_0 alone.
-constexpr int R3_XC = 32 * 128 * 4;                      // xc: [32 samples][32 chunks of 4 features] fp32
-static_assert(2 * FB_GPART + R3_XC == FB_BUF, "remat3 keeps k_bwd_remat2's tile buffer size");
-constexpr int R3_ENC_SLOTS = 3;                          // remat of tile k + 1 and wgrad of tile k, DMA of k + 2
+// still made per tile (the BatchNorm backward's x kk term), but only as that term: the W waves form
+// xc = x (kk invstd gamma 2^eo) + gm invstd gamma 2^eo in fp32 (no hi / mid split: x is not an MFMA operand),
+// and the epilogue is one fma, 2^eo g_{L-1} = dy A - xc.  Per SIMD and tile the matrix pipe carries 96 + 24 + 24 MFMA
+// groups.  The weight-gradient partials (per pair: 256 rows x the half's 32 encoding columns, in a 64-column layout,
+// WgradCfg<1>) are summed per row into the chunk's float64 G_d (gd_reduce_row) by the next launch's tail; k_gd_tail
+// sums layer 1's.  The skip layer's encoding columns ARE its G_d.
+constexpr int R3_XC = 32 * 128 * 4;   // the D waves' accumulators: [32 samples][32 chunks of 4 features] fp32
+static_assert(2 * FB_GPART + R3_XC == FB_BUF, "the tile buffer: g_L's two parts and the accumulator slot");
+constexpr int R3_ENC_SLOTS = 3;                          // remat and wgrad of tile k, tile k + 1 waiting, DMA of k + 2
 constexpr size_t R3_LDS = 2 * (size_t)FB_BUF + R3_ENC_SLOTS * FB_ENC + 8 * 128 * sizeof(float);
 static_assert(R3_LDS <= 160 * 1024, "k_bwd_remat3 LDS");
 // layer 1's launch with dW_0's encoding columns fused (LAST): a fourth encoding slot (tile k - 1's image stays until
@@ -4239,7 +4170,7 @@ static_assert(R3L_LDS <= 160 * 1024, "k_bwd_remat3<true, true> LDS");
 constexpr size_t GD_PART = WgradCfg<1>::PART;            // 256 x 64 + 256 floats per pair
 constexpr int GD_LAYER = 256 * 64;                       // doubles of one layer's G_d
 // 16-byte chunk c4 (features 4 c4 .. 4 c4 + 3) of sample s: 16 lanes of one k-group (16 samples) on 16 distinct bank
-// groups for the W waves' stores and the D waves' reads alike
+// groups for the D waves' stores and the W waves' reads alike
 __device__ __forceinline__ int r3_xoff(int s, int c4) { return s * 512 + 16 * (c4 ^ (s & 15)); }
 
 // Row m = blockIdx.x of a layer's G_d over np pair partials (WgradCfg<1> layout), float64, by NT threads: column
@@ -4272,31 +4203,23 @@ __device__ __forceinline__ void gd_reduce_row(const float* __restrict__ part, in
   __syncthreads();
 }
 
-// WEPI (version 4): the BatchNorm-backward epilogue and the g_{L-1} stores move from the D to the W waves, which
-// hold x in registers from their own rematerialisation: a D wave runs only the 96 data-gradient MFMAs of a tile and
-// writes its fp32 accumulators to LDS (the xc slot's 16 KiB), a W wave takes tile k - 1's accumulators there after
-// the barrier, finishes g_{L-1} = dy A - (x X + B) and stores it, then makes x of tile k and G_d of tile k (48 MFMAs):
-// per SIMD 96 MFMAs against 48 + the epilogue's VALU, instead of 96 + epilogue against 48.
+// The BatchNorm-backward epilogue and the g_{L-1} stores are on the W waves, which hold x in registers from their own
+// rematerialisation: a D wave runs only the 96 data-gradient MFMAs of a tile and writes its fp32 accumulators to LDS
+// (the R3_XC slot's 16 KiB), a W wave takes tile k - 1's accumulators there after the barrier, finishes
+// g_{L-1} = dy A - (x X + B) and stores it, then makes x of tile k and G_d of tile k (48 MFMAs): per SIMD 96 MFMAs
+// against 48 + the epilogue's VALU.
 //
-// LAST (layer 1, with WEPI): g_0 is consumed in the launch that makes it -- its only use is dW_0's encoding columns
+// LAST (layer 1): g_0 is consumed in the launch that makes it -- its only use is dW_0's encoding columns
 // G_0 = sum_s g_0 (x) d -- so the W waves write their g_0 cells of tile k - 1 to the LDS g_0 tile instead of HBM and
-// form G_0 there (24 more MFMAs: their 32 rows x the 64 encoding columns), one partial set per pair in
-// k_wgrad_enc's layout (part0): k_wgrad_enc and g_0's 1 KiB/sample round trip through HBM are gone.
-#ifndef PCN_R3_ABL
-#define PCN_R3_ABL 0    // timing-only ablations of k_bwd_remat3<true> (wrong results): 1 W waves idle, 2 D waves
-                        // without MFMAs, 3 D waves' B operands from registers instead of LDS, 4 no DMA waits
-#endif
-#ifndef PCN_R3_WORDER
-#define PCN_R3_WORDER 2   // W waves: G_d's transposed reads issued 1 after the epilogue / 2 before it (0: after remat)
-#endif
-#ifndef PCN_R3_DPF
-#define PCN_R3_DPF 0      // D waves: the next k-step's B operands read one k-step ahead into registers
-#endif
-#ifndef PCN_R3_KREG
-#define PCN_R3_KREG 1   // the W waves' per-feature epilogue / remat constants in registers (0: read from LDS, A/B)
-#endif
-template <bool WEPI, bool LAST = false, int NW = 4>
-__global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __restrict__ gin, char* __restrict__ gout,
+// form G_0 there (24 more MFMAs: their 32 rows x the 64 encoding columns), one partial set per pair in the same
+// 64-column layout (part0): g_0 makes no round trip through HBM.
+//
+// WEPI (the epilogue on the W waves) and NW (the number of W waves) are fixed at <true, ., 4>: the forms with the
+// epilogue on the D waves (remat version 3) and with eight W waves were measured slower and are retired (HISTORY.md).
+// The parameters stay because the instantiation names are what the profiles and the benchmark's kernel tags are
+// keyed by.
+template <bool WEPI, bool LAST, int NW>
+__global__ __launch_bounds__(512, 1) void k_bwd_remat3(const char* __restrict__ gin, char* __restrict__ gout,
                                                         const f16x8* __restrict__ wt,
                                                         const int* __restrict__ sw, int layer, int64_t n,
                                                         const float* __restrict__ coefp, const float* __restrict__ bnb,
@@ -4308,9 +4231,8 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
                                                         const char* __restrict__ enc,
                                                         const f16x8* __restrict__ px, const float* __restrict__ pxs,
                                                         const unsigned* __restrict__ pbound, float* __restrict__ part0) {
-  static_assert(!LAST || WEPI, "the fused layer-0 columns need the W-wave epilogue");
-  static_assert(NW == 4 || (NW == 8 && WEPI && !LAST), "eight W waves: the W-wave epilogue, hidden layers");
-  // NW W waves: FW features of the half each (RBW row blocks of 16) and GR rows of G_d (JBW blocks of 16)
+  static_assert(WEPI && NW == 4, "only the W-wave epilogue with four W waves is built");
+  // a W wave: FW features of the half (RBW row blocks of 16) and GR rows of G_d (JBW blocks of 16)
   constexpr int FW = 128 / NW, RBW = FW / 16, GR = 256 / NW, JBW = GR / 16;
   constexpr int NST = LAST ? 0 : 2 * RBW;   // a g-storing wave's global stores per tile
   constexpr int NS = LAST ? 4 : R3_ENC_SLOTS;   // encoding slots
@@ -4367,7 +4289,7 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
   __syncthreads();
   float obm = cst[896];
 #pragma unroll
-  for (int i = 1; i < 4 + NW; ++i) obm = fmaxf(obm, cst[896 + i]);
+  for (int i = 1; i < 8; ++i) obm = fmaxf(obm, cst[896 + i]);
   const int eo = tile_scale_exp(obm);
   const float gso = ldexpf(1.0f, eo);
   if (bid == 0 && t == 0) gexp[layer - 1] = eo;
@@ -4398,339 +4320,23 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
     asm volatile("" : "+v"(ln));
     fb_glds16(enc + (size_t)tl * FB_ENC + wv * 1024 + ln * 16, enb + (k % NS) * FB_ENC + wv * 1024);
   };
-  // W waves: xc of tile k, features 32 rw .. 32 rw + 31 of the half (2 row blocks of P'), enc slot k % 3 -> buffer k & 1
-  auto remat_xc = [&](int k) {
-    const char* eb = enb + (k % NS) * FB_ENC;
-    char* const xb = fb + (size_t)(k & 1) * FB_BUF + 2 * FB_GPART;
-    f32x4 ax[RBW][2];
-#pragma unroll
-    for (int rb = 0; rb < RBW; ++rb) ax[rb][0] = ax[rb][1] = f32x4{};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const auto& pa = pa_r[ks];
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const int o = fb_eoff(16 * sb + lm, 4 * ks + kg);
-        const f16x8 bh = *reinterpret_cast<const f16x8*>(eb + o);
-        const f16x8 bm = *reinterpret_cast<const f16x8*>(eb + FB_ENC / 2 + o);
-#pragma unroll
-        for (int rb = 0; rb < RBW; ++rb) {
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bh, ax[rb][sb], 0, 0, 0);
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bm, ax[rb][sb], 0, 0, 0);
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][1], bh, ax[rb][sb], 0, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int rb = 0; rb < RBW; ++rb) {
-      const int il = FW * rwW + 16 * rb + 4 * kg;
-      const f32x4 X = *reinterpret_cast<const f32x4*>(cst + 768 + il);
-      const f32x4 B = *reinterpret_cast<const f32x4*>(cst + 256 + il);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        f32x4 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = fmaf(ax[rb][sb][q], X[q], B[q]);
-        *reinterpret_cast<f32x4*>(xb + r3_xoff(16 * sb + lm, il >> 2)) = v;
-      }
-    }
-  };
   if (nk > 0) {
-    if (wv < 8) {   // (waves 8.. of the eight-W-wave form issue no DMA)
+    // (wv < 8 holds for all 512 threads; stated, it lets the compiler form the waves' DMA addresses without sign
+    // extension -- here and in the W waves' loop the emitted code depends on it, nothing else does: drop both
+    // guards whenever the kernel is next re-measured)
+    if (wv < 8) {
       dma_g(0);
       dma_enc(0);
       if (nk > 1) dma_enc(1);
     }
     __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
     __builtin_amdgcn_s_barrier();
-    if (!WEPI && wv >= 4) remat_xc(0);
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_s_barrier();
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  if constexpr (WEPI) {
-    if (wv < 4) {
-      // ---- D: the data-gradient MFMAs of features 128 hf + 32 rw + 16 rb + lm; accumulators to LDS
-      f16x8 wr[8][2][2];
-      {
-        const f16x8* __restrict__ w8 = wt + lane;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-          for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) wr[ks][rb][p] = w8[((ks * 16 + 8 * hf + 2 * rw + rb) * 2 + p) * 64];
-      }
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
-        asm volatile("" ::"v"(wr[ks][0][0]), "v"(wr[ks][0][1]), "v"(wr[ks][1][0]), "v"(wr[ks][1][1]));
-      constexpr int ABL = LAST ? 0 : PCN_R3_ABL;
-      for (int k = 0; k < nk; ++k) {
-        if (k + 1 < nk) dma_g(k + 1);
-        if (k + 2 < nk) dma_enc(k + 2);
-        char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-        f32x4 ad[2][2] = {{f32x4{}, f32x4{}}, {f32x4{}, f32x4{}}};
-        constexpr bool DPF = !LAST && PCN_R3_DPF;
-        f16x8 bq[2][2][2];   // DPF: [k-step parity][sb][part], the next k-step's operands read ahead
-        auto bload = [&](int ks) {
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb) {
-            const int o = gs_off(16 * sb + lm, 4 * ks + kg);
-            bq[ks & 1][sb][0] = *reinterpret_cast<const f16x8*>(sp + o);
-            bq[ks & 1][sb][1] = *reinterpret_cast<const f16x8*>(sp + FB_GPART + o);
-          }
-        };
-        if (DPF) bload(0);
-#pragma unroll
-        for (int ks = 0; ks < (ABL == 2 ? 0 : 8); ++ks) {
-          if (DPF && ks + 1 < 8) bload(ks + 1);
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb) {
-            const int o = gs_off(16 * sb + lm, 4 * ks + kg);
-            const f16x8 bh = DPF ? bq[ks & 1][sb][0] : ABL == 3 ? wr[(ks + 1) & 7][sb][0]
-                                                               : *reinterpret_cast<const f16x8*>(sp + o);
-            const f16x8 bm = DPF ? bq[ks & 1][sb][1] : ABL == 3 ? wr[(ks + 2) & 7][sb][1]
-                                                               : *reinterpret_cast<const f16x8*>(sp + FB_GPART + o);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-              ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][0], bh, ad[rb][sb], 0, 0, 0);
-              ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][0], bm, ad[rb][sb], 0, 0, 0);
-              ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][1], bh, ad[rb][sb], 0, 0, 0);
-            }
-          }
-        }
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb)
-            *reinterpret_cast<f32x4*>(sp + 2 * FB_GPART + r3_xoff(16 * sb + lm, (32 * rw + 16 * rb + 4 * kg) >> 2)) =
-                ad[rb][sb];
-        if (ABL != 4) __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-      }
-    } else {
-      // ---- W: epilogue + stores of tile k - 1, x of tile k (registers), G_d of tile k
-      const float gui = ldexpf(1.0f, -eo);
-      float gmo = 0.0f;
-      f32x4 xr[RBW][2];   // x X + B of the previous tile
-#pragma unroll
-      for (int rb = 0; rb < RBW; ++rb) xr[rb][0] = xr[rb][1] = f32x4{};
-      f32x4 aw[JBW][2];
-#pragma unroll
-      for (int jb = 0; jb < JBW; ++jb)
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib) aw[jb][ib] = f32x4{};
-      const int trq = lm >> 2, trp = lm & 3, tr0 = 8 * kg + trq, tr1 = tr0 + 4;
-      auto join = [](const s16x4& a, const s16x4& b) {
-        return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-      };
-      auto eoff = [](int r, int c) { return r * 128 + 16 * ((c >> 3) ^ ((r >> 1) & 7)) + 2 * (c & 7); };
-      // the epilogue's and the remat's per-feature constants A, X, B of this wave's 2 x 4 features: in registers
-      // for the launch (24 VGPRs; 6 KiB of LDS reads per wave and tile saved), except in layer 1's fused launch,
-      // whose G_0 accumulators take those registers
-      f32x4 kA[RBW], kX[RBW], kB[RBW];
-#pragma unroll
-      for (int rb = 0; rb < RBW; ++rb) {
-        const int il = FW * rwW + 16 * rb + 4 * kg;
-        kA[rb] = *reinterpret_cast<const f32x4*>(cst + 640 + il);
-        kX[rb] = *reinterpret_cast<const f32x4*>(cst + 768 + il);
-        kB[rb] = *reinterpret_cast<const f32x4*>(cst + 256 + il);
-      }
-      constexpr bool KREG = PCN_R3_KREG && !LAST;
-      auto cA_of = [&](int rb, int il) { return KREG ? kA[rb] : *reinterpret_cast<const f32x4*>(cst + 640 + il); };
-      auto cX_of = [&](int rb, int il) { return KREG ? kX[rb] : *reinterpret_cast<const f32x4*>(cst + 768 + il); };
-      auto cB_of = [&](int rb, int il) { return KREG ? kB[rb] : *reinterpret_cast<const f32x4*>(cst + 256 + il); };
-      // tile kq's g_{L-1}: its accumulators (LDS) and xr; kq < 0: zero cells to tile 0's own slots (rewritten by
-      // this wave's later stores -- same addresses, program order), so every tile has NST stores behind its DMAs
-      auto epilogue = [&](int kq) {
-        if (LAST && kq < 0) return;
-        const int tq = pr + (kq < 0 ? 0 : kq) * npair;
-        const char* adb = fb + (size_t)((kq < 0 ? 0 : kq) & 1) * FB_BUF + 2 * FB_GPART;
-#pragma unroll
-        for (int rb = 0; rb < RBW; ++rb) {
-          const int il = FW * rwW + 16 * rb + 4 * kg, i = 128 * hf + il;
-          const f32x4 cA = cA_of(rb, il);
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb) {
-            const int sm = 16 * sb + lm;
-            const bool valid = kq >= 0 && (int64_t)tq * 32 + sm < n;
-            const f32x4 ad = *reinterpret_cast<const f32x4*>(adb + r3_xoff(sm, il >> 2));
-            f32x4 vs;   // 2^eo g_{L-1}
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              vs[q] = valid ? fmaf(ad[q], cA[q], -xr[rb][sb][q]) : 0.0f;
-              gmo = fmaxf(gmo, fabsf(vs[q]));
-            }
-            s16x4 p0, p1;
-            split2_x4(vs, p0, p1);
-            const fb_i32x2 hv = __builtin_bit_cast(fb_i32x2, p0), mv = __builtin_bit_cast(fb_i32x2, p1);
-            const auto s0 = __builtin_amdgcn_permlane16_swap(hv[0], mv[0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(hv[1], mv[1], false, false);
-            const u32x4 cell = {s0[0], s1[0], s0[1], s1[1]};
-            if constexpr (LAST) {
-              *reinterpret_cast<u32x4*>(g0i + (kg & 1) * (R3_G0 / 2) + gs_off(sm, il >> 3)) = cell;
-            } else {
-              char* gt = gout + (size_t)tq * GS_TILE + (kg & 1) * FB_GPART + gs_off(sm, i >> 3);
-              __builtin_nontemporal_store(cell, reinterpret_cast<u32x4*>(gt));
-            }
-          }
-        }
-      };
-      // LAST: G_0 of tile kq, rows 32 rw + 16 jb + 4 kg + r of the half's g_0 (this wave's own epilogue rows, read
-      // back transposed from the g_0 tile) x the 64 encoding columns of tile kq's image (slot kq % 4)
-      f32x4 a0w[2][4];
-#pragma unroll
-      for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) a0w[jb][ib] = f32x4{};
-      auto gd0 = [&](int kq) {
-        asm volatile("" ::: "memory");   // the g_0 cell stores above, before the transposed reads
-        const unsigned g0a = fb_lds_addr(g0i), ea = fb_lds_addr(enb + (kq % NS) * FB_ENC);
-        std::array<s16x4, 4> ra[2], rx[4];
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-          const int col = 32 * rw + 16 * jb + 4 * trp;
-          const unsigned a0 = g0a + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = g0a + gs_off(tr1, col >> 3) + 2 * (col & 7);
-          ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<R3_G0 / 2>(a0), fb_tr<R3_G0 / 2>(a1)};
-        }
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-          const int c = 16 * ib + 4 * trp;
-          const unsigned a0 = ea + eoff(tr0, c), a1 = ea + eoff(tr1, c);
-          rx[ib] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_ENC / 2>(a0), fb_tr<FB_ENC / 2>(a1)};
-        }
-        fb_lgkm<0>(ra);
-        fb_lgkm<0>(rx);
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-          const f16x8 B0 = join(rx[ib][0], rx[ib][1]), B1 = join(rx[ib][2], rx[ib][3]);
-#pragma unroll
-          for (int jb = 0; jb < 2; ++jb) {
-            const f16x8 A0 = join(ra[jb][0], ra[jb][1]), A1 = join(ra[jb][2], ra[jb][3]);
-            a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, a0w[jb][ib], 0, 0, 0);
-            a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1, a0w[jb][ib], 0, 0, 0);
-            a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0, a0w[jb][ib], 0, 0, 0);
-          }
-        }
-        asm volatile("" ::: "memory");   // the reads above, before the next tile's cell stores
-      };
-      auto remat_reg = [&](int k) {
-        const char* eb = enb + (k % NS) * FB_ENC;
-        f32x4 ax[RBW][2];
-#pragma unroll
-        for (int rb = 0; rb < RBW; ++rb) ax[rb][0] = ax[rb][1] = f32x4{};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const auto& pa = pa_r[ks];
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb) {
-            const int o = fb_eoff(16 * sb + lm, 4 * ks + kg);
-            const f16x8 bh = *reinterpret_cast<const f16x8*>(eb + o);
-            const f16x8 bm = *reinterpret_cast<const f16x8*>(eb + FB_ENC / 2 + o);
-#pragma unroll
-            for (int rb = 0; rb < RBW; ++rb) {
-              ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bh, ax[rb][sb], 0, 0, 0);
-              ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bm, ax[rb][sb], 0, 0, 0);
-              ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][1], bh, ax[rb][sb], 0, 0, 0);
-            }
-          }
-        }
-#pragma unroll
-        for (int rb = 0; rb < RBW; ++rb) {
-          const int il = FW * rwW + 16 * rb + 4 * kg;
-          const f32x4 X = cX_of(rb, il), B = cB_of(rb, il);
-#pragma unroll
-          for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xr[rb][sb][q] = fmaf(ax[rb][sb][q], X[q], B[q]);
-        }
-      };
-      constexpr int ABLW = LAST ? 0 : PCN_R3_ABL;
-      for (int k = 0; k < nk; ++k) {
-        if (wv < 8 && k + 1 < nk) dma_g(k + 1);
-        if (wv < 8 && k + 2 < nk) dma_enc(k + 2);
-        if (ABLW == 1) {
-          __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
-          __builtin_amdgcn_s_waitcnt(0xC07F);
-          __builtin_amdgcn_s_barrier();
-          continue;
-        }
-        const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-        const unsigned ga = fb_lds_addr(sp), ea = fb_lds_addr(enb + (k % NS) * FB_ENC);
-        std::array<s16x4, 4> ra[JBW], rx[2];
-        auto gd_reads = [&]() {
-#pragma unroll
-          for (int jb = 0; jb < JBW; ++jb) {
-            const int col = GR * rwW + 16 * jb + 4 * trp;
-            const unsigned a0 = ga + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = ga + gs_off(tr1, col >> 3) + 2 * (col & 7);
-            ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_GPART>(a0), fb_tr<FB_GPART>(a1)};
-          }
-#pragma unroll
-          for (int ib = 0; ib < 2; ++ib) {
-            const int c = 32 * hf + 16 * ib + 4 * trp;
-            const unsigned a0 = ea + eoff(tr0, c), a1 = ea + eoff(tr1, c);
-            rx[ib] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_ENC / 2>(a0), fb_tr<FB_ENC / 2>(a1)};
-          }
-          asm volatile("" ::: "memory");   // (issued before the LDS reads that follow)
-        };
-        constexpr int WO = LAST ? 0 : PCN_R3_WORDER;
-        if (WO == 2) gd_reads();
-        epilogue(k - 1);
-        if (LAST && k > 0) gd0(k - 1);
-        if (WO == 1) gd_reads();
-        remat_reg(k);
-        if (WO == 0) gd_reads();
-        fb_lgkm<0>(ra);
-        fb_lgkm<0>(rx);
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib) {
-          const f16x8 B0 = join(rx[ib][0], rx[ib][1]), B1 = join(rx[ib][2], rx[ib][3]);
-#pragma unroll
-          for (int jb = 0; jb < JBW; ++jb) {
-            const f16x8 A0 = join(ra[jb][0], ra[jb][1]), A1 = join(ra[jb][2], ra[jb][3]);
-            aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, aw[jb][ib], 0, 0, 0);
-            aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1, aw[jb][ib], 0, 0, 0);
-            aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0, aw[jb][ib], 0, 0, 0);
-          }
-        }
-        if (ABLW != 4) __builtin_amdgcn_s_waitcnt(fb_vmcnt(NST));   // this wave's DMAs (its stores may fly)
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_s_barrier();
-      }
-      if (nk > 0) epilogue(nk - 1);   // (the loop's last barrier: D's accumulators of tile nk - 1 are in LDS)
-      if (LAST && nk > 0) gd0(nk - 1);
-      gmo = wave_max_f(gmo) * gui;
-      if (lane == 0) atomicMax(gmax_out + ((bid * 4 + rwW) & (GMAX_SLOTS - 1)), __float_as_uint(gmo));
-      float* const pb = part + (size_t)pr * GD_PART;
-      const int sxyz = remat_sx(0, __uint_as_float(*pbound));
-#pragma unroll
-      for (int ib = 0; ib < 2; ++ib) {
-        const int col = 32 * hf + 16 * ib + lm;
-        const float cu = ldexpf(gun, -(col < 3 ? sxyz : 13));
-#pragma unroll
-        for (int jb = 0; jb < JBW; ++jb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) pb[(size_t)(GR * rwW + 16 * jb + 4 * kg + r) * 64 + col] = aw[jb][ib][r] * cu;
-      }
-      if constexpr (LAST) {   // G_0, unscaled (2^-eo of the g_0 tile, 2^-s of the column); the bias row: exact 0
-        float* const p0 = part0 + (size_t)pr * GD_PART;
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-          const int col = 16 * ib + lm;
-          const float cu = ldexpf(gui, -(col < 3 ? sxyz : 13));
-#pragma unroll
-          for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              p0[(size_t)(128 * hf + 32 * rw + 16 * jb + 4 * kg + r) * 64 + col] = a0w[jb][ib][r] * cu;
-        }
-        if (lane < 32) p0[(size_t)256 * 64 + 128 * hf + 32 * rw + lane] = 0.0f;
-      }
-    }
-  } else if (wv < 4) {
-    // ---- D: data gradient of input features 128 hf + 32 rw + 16 rb + lm, epilogue, g_{L-1} stores
-    const float gui = ldexpf(1.0f, -eo);
+  if (wv < 4) {
+    // ---- D: the data-gradient MFMAs of features 128 hf + 32 rw + 16 rb + lm; accumulators to LDS
     f16x8 wr[8][2][2];
     {
       const f16x8* __restrict__ w8 = wt + lane;
@@ -4744,25 +4350,13 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
       asm volatile("" ::"v"(wr[ks][0][0]), "v"(wr[ks][0][1]), "v"(wr[ks][1][0]), "v"(wr[ks][1][1]));
-    float gmo = 0.0f;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 pcell[2][2] = {{u32x4{}, u32x4{}}, {u32x4{}, u32x4{}}};
-    auto store_cell = [&](int rb, int sb, int tq, const u32x4& cell) {
-      const int i = 128 * hf + 32 * rw + 16 * rb + 4 * kg, sm = 16 * sb + lm;
-      char* gt = gout + (size_t)tq * GS_TILE + (kg & 1) * FB_GPART + gs_off(sm, i >> 3);
-      __builtin_nontemporal_store(cell, reinterpret_cast<u32x4*>(gt));
-    };
-    // tile k's g_{L-1} cells are stored during tile k + 1's data-gradient MFMAs (k_bwd_remat2's schedule)
     for (int k = 0; k < nk; ++k) {
-      const int tl = pr + k * npair;
-      const int ptl = k > 0 ? tl - npair : tl;
       if (k + 1 < nk) dma_g(k + 1);
       if (k + 2 < nk) dma_enc(k + 2);
-      const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-      const char* xb = sp + 2 * FB_GPART;
+      char* const sp = fb + (size_t)(k & 1) * FB_BUF;
       f32x4 ad[2][2] = {{f32x4{}, f32x4{}}, {f32x4{}, f32x4{}}};
 #pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
+      for (int ks = 0; ks < 8; ++ks) {
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
           const int o = gs_off(16 * sb + lm, 4 * ks + kg);
@@ -4774,51 +4368,28 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
             ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][0], bm, ad[rb][sb], 0, 0, 0);
             ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][1], bh, ad[rb][sb], 0, 0, 0);
           }
-          if ((ks & 1) && sb == 1) {
-            store_cell((ks >> 2) & 1, (ks >> 1) & 1, ptl, pcell[(ks >> 2) & 1][(ks >> 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-        const int il = 32 * rw + 16 * rb + 4 * kg;
-        const f32x4 cA = *reinterpret_cast<const f32x4*>(cst + 640 + il);
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-          const int sm = 16 * sb + lm;
-          const bool valid = (int64_t)tl * 32 + sm < n;
-          const f32x4 xc = *reinterpret_cast<const f32x4*>(xb + r3_xoff(sm, il >> 2));
-          f32x4 vs;   // 2^eo g_{L-1}
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            vs[q] = valid ? fmaf(ad[rb][sb][q], cA[q], -xc[q]) : 0.0f;
-            gmo = fmaxf(gmo, fabsf(vs[q]));
-          }
-          s16x4 p0, p1;
-          split2_x4(vs, p0, p1);
-          const fb_i32x2 hv = __builtin_bit_cast(fb_i32x2, p0), mv = __builtin_bit_cast(fb_i32x2, p1);
-          const auto s0 = __builtin_amdgcn_permlane16_swap(hv[0], mv[0], false, false);
-          const auto s1 = __builtin_amdgcn_permlane16_swap(hv[1], mv[1], false, false);
-          pcell[rb][sb] = u32x4{s0[0], s1[0], s0[1], s1[1]};
         }
       }
-      __builtin_amdgcn_s_waitcnt(fb_vmcnt(NST));   // this wave's DMAs (its stores may fly)
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-    }
-    if (nk > 0) {   // the last tile's cells
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-        for (int sb = 0; sb < 2; ++sb) store_cell(rb, sb, pr + (nk - 1) * npair, pcell[rb][sb]);
+        for (int sb = 0; sb < 2; ++sb)
+          *reinterpret_cast<f32x4*>(sp + 2 * FB_GPART + r3_xoff(16 * sb + lm, (32 * rw + 16 * rb + 4 * kg) >> 2)) =
+              ad[rb][sb];
+      __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_s_barrier();
     }
-    gmo = wave_max_f(gmo) * gui;
-    if (lane == 0) atomicMax(gmax_out + ((bid * 4 + rw) & (GMAX_SLOTS - 1)), __float_as_uint(gmo));
   } else {
-    // ---- W: xc of tile k + 1; G_d rows j = 64 rw + 16 jb + lm (4 blocks) x the half's 32 encoding columns
-    f32x4 aw[4][2];
+    // ---- W: epilogue + stores of tile k - 1, x of tile k (registers), G_d of tile k
+    const float gui = ldexpf(1.0f, -eo);
+    float gmo = 0.0f;
+    f32x4 xr[RBW][2];   // x X + B of the previous tile
 #pragma unroll
-    for (int jb = 0; jb < 4; ++jb)
+    for (int rb = 0; rb < RBW; ++rb) xr[rb][0] = xr[rb][1] = f32x4{};
+    f32x4 aw[JBW][2];
+#pragma unroll
+    for (int jb = 0; jb < JBW; ++jb)
 #pragma unroll
       for (int ib = 0; ib < 2; ++ib) aw[jb][ib] = f32x4{};
     const int trq = lm >> 2, trp = lm & 3, tr0 = 8 * kg + trq, tr1 = tr0 + 4;
@@ -4826,43 +4397,174 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
       return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
     };
     auto eoff = [](int r, int c) { return r * 128 + 16 * ((c >> 3) ^ ((r >> 1) & 7)) + 2 * (c & 7); };
-    for (int k = 0; k < nk; ++k) {
-      if (k + 1 < nk) dma_g(k + 1);
-      if (k + 2 < nk) dma_enc(k + 2);
-      if (k + 1 < nk) remat_xc(k + 1);
-      const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-      const unsigned ga = fb_lds_addr(sp), ea = fb_lds_addr(enb + (k % NS) * FB_ENC);
-      std::array<s16x4, 4> ra[4], rx[2];
+    // the epilogue's and the remat's per-feature constants A, X, B of this wave's 2 x 4 features: in registers
+    // for the launch (24 VGPRs; 6 KiB of LDS reads per wave and tile saved), except in layer 1's fused launch,
+    // whose G_0 accumulators take those registers
+    f32x4 kA[RBW], kX[RBW], kB[RBW];
 #pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const int col = 64 * rw + 16 * jb + 4 * trp;
-        const unsigned a0 = ga + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = ga + gs_off(tr1, col >> 3) + 2 * (col & 7);
-        ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_GPART>(a0), fb_tr<FB_GPART>(a1)};
+    for (int rb = 0; rb < RBW; ++rb) {
+      const int il = FW * rwW + 16 * rb + 4 * kg;
+      kA[rb] = *reinterpret_cast<const f32x4*>(cst + 640 + il);
+      kX[rb] = *reinterpret_cast<const f32x4*>(cst + 768 + il);
+      kB[rb] = *reinterpret_cast<const f32x4*>(cst + 256 + il);
+    }
+    constexpr bool KREG = !LAST;
+    auto cA_of = [&](int rb, int il) { return KREG ? kA[rb] : *reinterpret_cast<const f32x4*>(cst + 640 + il); };
+    auto cX_of = [&](int rb, int il) { return KREG ? kX[rb] : *reinterpret_cast<const f32x4*>(cst + 768 + il); };
+    auto cB_of = [&](int rb, int il) { return KREG ? kB[rb] : *reinterpret_cast<const f32x4*>(cst + 256 + il); };
+    // tile kq's g_{L-1}: its accumulators (LDS) and xr; kq < 0: zero cells to tile 0's own slots (rewritten by
+    // this wave's later stores -- same addresses, program order), so every tile has NST stores behind its DMAs
+    auto epilogue = [&](int kq) {
+      if (LAST && kq < 0) return;
+      const int tq = pr + (kq < 0 ? 0 : kq) * npair;
+      const char* adb = fb + (size_t)((kq < 0 ? 0 : kq) & 1) * FB_BUF + 2 * FB_GPART;
+#pragma unroll
+      for (int rb = 0; rb < RBW; ++rb) {
+        const int il = FW * rwW + 16 * rb + 4 * kg, i = 128 * hf + il;
+        const f32x4 cA = cA_of(rb, il);
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) {
+          const int sm = 16 * sb + lm;
+          const bool valid = kq >= 0 && (int64_t)tq * 32 + sm < n;
+          const f32x4 ad = *reinterpret_cast<const f32x4*>(adb + r3_xoff(sm, il >> 2));
+          f32x4 vs;   // 2^eo g_{L-1}
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            vs[q] = valid ? fmaf(ad[q], cA[q], -xr[rb][sb][q]) : 0.0f;
+            gmo = fmaxf(gmo, fabsf(vs[q]));
+          }
+          s16x4 p0, p1;
+          split2_x4(vs, p0, p1);
+          const fb_i32x2 hv = __builtin_bit_cast(fb_i32x2, p0), mv = __builtin_bit_cast(fb_i32x2, p1);
+          const auto s0 = __builtin_amdgcn_permlane16_swap(hv[0], mv[0], false, false);
+          const auto s1 = __builtin_amdgcn_permlane16_swap(hv[1], mv[1], false, false);
+          const u32x4 cell = {s0[0], s1[0], s0[1], s1[1]};
+          if constexpr (LAST) {
+            *reinterpret_cast<u32x4*>(g0i + (kg & 1) * (R3_G0 / 2) + gs_off(sm, il >> 3)) = cell;
+          } else {
+            char* gt = gout + (size_t)tq * GS_TILE + (kg & 1) * FB_GPART + gs_off(sm, i >> 3);
+            __builtin_nontemporal_store(cell, reinterpret_cast<u32x4*>(gt));
+          }
+        }
+      }
+    };
+    // LAST: G_0 of tile kq, rows 32 rw + 16 jb + 4 kg + r of the half's g_0 (this wave's own epilogue rows, read
+    // back transposed from the g_0 tile) x the 64 encoding columns of tile kq's image (slot kq % 4)
+    f32x4 a0w[2][4];
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+      for (int ib = 0; ib < 4; ++ib) a0w[jb][ib] = f32x4{};
+    auto gd0 = [&](int kq) {
+      asm volatile("" ::: "memory");   // the g_0 cell stores above, before the transposed reads
+      const unsigned g0a = fb_lds_addr(g0i), ea = fb_lds_addr(enb + (kq % NS) * FB_ENC);
+      std::array<s16x4, 4> ra[2], rx[4];
+#pragma unroll
+      for (int jb = 0; jb < 2; ++jb) {
+        const int col = 32 * rw + 16 * jb + 4 * trp;
+        const unsigned a0 = g0a + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = g0a + gs_off(tr1, col >> 3) + 2 * (col & 7);
+        ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<R3_G0 / 2>(a0), fb_tr<R3_G0 / 2>(a1)};
       }
 #pragma unroll
-      for (int ib = 0; ib < 2; ++ib) {
-        const int c = 32 * hf + 16 * ib + 4 * trp;
+      for (int ib = 0; ib < 4; ++ib) {
+        const int c = 16 * ib + 4 * trp;
         const unsigned a0 = ea + eoff(tr0, c), a1 = ea + eoff(tr1, c);
         rx[ib] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_ENC / 2>(a0), fb_tr<FB_ENC / 2>(a1)};
       }
       fb_lgkm<0>(ra);
       fb_lgkm<0>(rx);
 #pragma unroll
+      for (int ib = 0; ib < 4; ++ib) {
+        const f16x8 B0 = join(rx[ib][0], rx[ib][1]), B1 = join(rx[ib][2], rx[ib][3]);
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb) {
+          const f16x8 A0 = join(ra[jb][0], ra[jb][1]), A1 = join(ra[jb][2], ra[jb][3]);
+          a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, a0w[jb][ib], 0, 0, 0);
+          a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1, a0w[jb][ib], 0, 0, 0);
+          a0w[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0, a0w[jb][ib], 0, 0, 0);
+        }
+      }
+      asm volatile("" ::: "memory");   // the reads above, before the next tile's cell stores
+    };
+    auto remat_reg = [&](int k) {
+      const char* eb = enb + (k % NS) * FB_ENC;
+      f32x4 ax[RBW][2];
+#pragma unroll
+      for (int rb = 0; rb < RBW; ++rb) ax[rb][0] = ax[rb][1] = f32x4{};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const auto& pa = pa_r[ks];
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) {
+          const int o = fb_eoff(16 * sb + lm, 4 * ks + kg);
+          const f16x8 bh = *reinterpret_cast<const f16x8*>(eb + o);
+          const f16x8 bm = *reinterpret_cast<const f16x8*>(eb + FB_ENC / 2 + o);
+#pragma unroll
+          for (int rb = 0; rb < RBW; ++rb) {
+            ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bh, ax[rb][sb], 0, 0, 0);
+            ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bm, ax[rb][sb], 0, 0, 0);
+            ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][1], bh, ax[rb][sb], 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int rb = 0; rb < RBW; ++rb) {
+        const int il = FW * rwW + 16 * rb + 4 * kg;
+        const f32x4 X = cX_of(rb, il), B = cB_of(rb, il);
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) xr[rb][sb][q] = fmaf(ax[rb][sb][q], X[q], B[q]);
+      }
+    };
+    for (int k = 0; k < nk; ++k) {
+      if (wv < 8 && k + 1 < nk) dma_g(k + 1);
+      if (wv < 8 && k + 2 < nk) dma_enc(k + 2);
+      const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
+      const unsigned ga = fb_lds_addr(sp), ea = fb_lds_addr(enb + (k % NS) * FB_ENC);
+      std::array<s16x4, 4> ra[JBW], rx[2];
+      auto gd_reads = [&]() {
+#pragma unroll
+        for (int jb = 0; jb < JBW; ++jb) {
+          const int col = GR * rwW + 16 * jb + 4 * trp;
+          const unsigned a0 = ga + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = ga + gs_off(tr1, col >> 3) + 2 * (col & 7);
+          ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_GPART>(a0), fb_tr<FB_GPART>(a1)};
+        }
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib) {
+          const int c = 32 * hf + 16 * ib + 4 * trp;
+          const unsigned a0 = ea + eoff(tr0, c), a1 = ea + eoff(tr1, c);
+          rx[ib] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_ENC / 2>(a0), fb_tr<FB_ENC / 2>(a1)};
+        }
+        asm volatile("" ::: "memory");   // (issued before the LDS reads that follow)
+      };
+      // G_d's transposed reads are issued before the epilogue; in layer 1's fused launch after the remat
+      if (!LAST) gd_reads();
+      epilogue(k - 1);
+      if (LAST && k > 0) gd0(k - 1);
+      remat_reg(k);
+      if (LAST) gd_reads();
+      fb_lgkm<0>(ra);
+      fb_lgkm<0>(rx);
+#pragma unroll
       for (int ib = 0; ib < 2; ++ib) {
         const f16x8 B0 = join(rx[ib][0], rx[ib][1]), B1 = join(rx[ib][2], rx[ib][3]);
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
+        for (int jb = 0; jb < JBW; ++jb) {
           const f16x8 A0 = join(ra[jb][0], ra[jb][1]), A1 = join(ra[jb][2], ra[jb][3]);
           aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, aw[jb][ib], 0, 0, 0);
           aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1, aw[jb][ib], 0, 0, 0);
           aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0, aw[jb][ib], 0, 0, 0);
         }
       }
-      __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
+      __builtin_amdgcn_s_waitcnt(fb_vmcnt(NST));   // this wave's DMAs (its stores may fly)
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_s_barrier();
     }
-    // this pair's G_d partial, unscaled (2^-gexp[L] of g_L, 2^-s_k of the column): Sigma_s g_L d_k
+    if (nk > 0) epilogue(nk - 1);   // (the loop's last barrier: D's accumulators of tile nk - 1 are in LDS)
+    if (LAST && nk > 0) gd0(nk - 1);
+    gmo = wave_max_f(gmo) * gui;
+    if (lane == 0) atomicMax(gmax_out + ((bid * 4 + rwW) & (GMAX_SLOTS - 1)), __float_as_uint(gmo));
     float* const pb = part + (size_t)pr * GD_PART;
     const int sxyz = remat_sx(0, __uint_as_float(*pbound));
 #pragma unroll
@@ -4870,18 +4572,32 @@ __global__ __launch_bounds__(64 * (4 + NW), 1) void k_bwd_remat3(const char* __r
       const int col = 32 * hf + 16 * ib + lm;
       const float cu = ldexpf(gun, -(col < 3 ? sxyz : 13));
 #pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
+      for (int jb = 0; jb < JBW; ++jb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pb[(size_t)(64 * rw + 16 * jb + 4 * kg + r) * 64 + col] = aw[jb][ib][r] * cu;
+        for (int r = 0; r < 4; ++r) pb[(size_t)(GR * rwW + 16 * jb + 4 * kg + r) * 64 + col] = aw[jb][ib][r] * cu;
+    }
+    if constexpr (LAST) {   // G_0, unscaled (2^-eo of the g_0 tile, 2^-s of the column); the bias row: exact 0
+      float* const p0 = part0 + (size_t)pr * GD_PART;
+#pragma unroll
+      for (int ib = 0; ib < 4; ++ib) {
+        const int col = 16 * ib + lm;
+        const float cu = ldexpf(gui, -(col < 3 ? sxyz : 13));
+#pragma unroll
+        for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            p0[(size_t)(128 * hf + 32 * rw + 16 * jb + 4 * kg + r) * 64 + col] = a0w[jb][ib][r] * cu;
+      }
+      if (lane < 32) p0[(size_t)256 * 64 + 128 * hf + 32 * rw + lane] = 0.0f;
     }
   }
   // the previous layer's G_d partials, one row per workgroup (LDS as scratch)
   __syncthreads();
-  if (rpart) gd_reduce_row<64 * (4 + NW)>(rpart, FB_PAIRS, rgd, reinterpret_cast<double*>(fb), t);
+  if (rpart) gd_reduce_row<512>(rpart, FB_PAIRS, rgd, reinterpret_cast<double*>(fb), t);
 }
 
-// after layer 1's launch: layer 1's G_d (grid.y 0) and layer 0's encoding columns from k_wgrad_enc's g_0 sets
-// (grid.y 1: dW_0, db_0), one row per block of 1024
+// after layer 1's launch: layer 1's G_d (grid.y 0) and layer 0's encoding columns from that launch's G_0 partial
+// sets (grid.y 1: dW_0, db_0), one row per block of 1024
 __global__ __launch_bounds__(1024) void k_gd_tail(const float* __restrict__ part1, double* __restrict__ gd1,
                                                   const float* __restrict__ pe0, double* __restrict__ dW0,
                                                   double* __restrict__ db0, int we) {
@@ -5355,17 +5071,15 @@ static void fused_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs&
 }
 
 // k_bwd_remat3's layers of one chunk (after k_g7): layers 7..1 (each launch's tail sums the previous layer's G_d
-// partials into ws.gd), k_wgrad_enc on g_0 alone, k_gd_tail (layer 1's G_d, dW_0), k_gd_proj (every layer's
-// dW_L += alpha (G_d P'^T), and the skip layer's encoding columns)
+// partials into ws.gd; layer 1's also forms dW_0's encoding columns), k_gd_tail (layer 1's G_d, dW_0), k_gd_proj
+// (every layer's dW_L += alpha (G_d P'^T), and the skip layer's encoding columns)
 template <class PR, class PS>
-static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB, const f16x8*,
-                          const float*, int64_t ci, int64_t n, const float*, hipStream_t s, char* encimg,
-                          const PR& prow, const PS& psrow, char* const (&S)[2], char* S2, float* const (&pset)[2]) {
+static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
+                          int64_t ci, int64_t n, hipStream_t s, char* encimg, const PR& prow, const PS& psrow,
+                          char* const (&S)[2], char* S2, float* const (&pset)[2]) {
   const double dn = (double)n;
-  const int64_t ntiles = (n + 31) / 32;
   const unsigned fbg = (unsigned)(2 * FB_PAIRS);
   float* const part_e0 = ws.part + 2 * (size_t)FB_PAIRS * WgradCfg<2>::PART;
-  const bool fuse0 = g_remat_ver == 4 && g_remat_fuse0;   // layer 1's launch forms dW_0's encoding columns
   for (int L = 7; L >= 1; --L) {
     const float* coefp = ws.coef + 1024 * (L - 1);
     const char* gin = L == 4 ? S2 : S[(7 - L) & 1];
@@ -5377,35 +5091,25 @@ static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdW
     // (2 x 256 x 256: G_L = sum g (x) x, formed here as (sum g (x) d) P'^T); issued on the matrix pipe per sample:
     // 2 x 256 x 256 + 2 x 256 x 64 (G_d) + 2 x 256 x 64 (x), x 3 products.  Bytes: g_L in (1 KiB), the encoding
     // image (256 B), g_{L-1} out (1 KiB)
-    // (layer 1 fused: + 2 x 256 x 64 of dW_0's encoding columns; g_0 stays in LDS: 1 KiB less out)
-    const bool last = fuse0 && L == 1;
+    // (layer 1: + 2 x 256 x 64 of dW_0's encoding columns; g_0 stays in LDS: 1 KiB less out)
+    const bool last = L == 1;
     ProfScope ps(s, last ? PT_BWD_FUSED_L1 : PT_BWD_FUSED,
                  (2.0 * 2.0 * 256.0 * 256.0 + (last ? 2.0 * 256.0 * 64.0 : 0.0)) * dn,
                  (1024.0 + 256.0 + (last ? 0.0 : 1024.0)) * dn);
-    auto launch = [&](auto kern, size_t lds, unsigned threads = 512) {
-      hipLaunchKernelGGL(kern, dim3(fbg), dim3(threads), lds, s, gin, gout, ws.wth16 + (size_t)(L - 1) * HW_H,
+    auto launch = [&](auto kern, size_t lds) {
+      hipLaunchKernelGGL(kern, dim3(fbg), dim3(512), lds, s, gin, gout, ws.wth16 + (size_t)(L - 1) * HW_H,
                          (const int*)ws.sw, L, n, coefp, (const float*)(ws.bnb + 512 * (L - 1)), P.bn_w[L - 1],
                          ws.gexp, (const float*)(ws.wcol + (L - 1) * 256), gmin, ws.gmax + (L - 1) * GMAX_SLOTS,
                          pset[L & 1], rpart, rgd, (const char*)encimg, prow(L - 1), psrow(L - 1),
                          (const unsigned*)ws.pbound, last ? part_e0 : (float*)nullptr);
     };
-    if (last) launch(k_bwd_remat3<true, true>, R3L_LDS);
-    else if (g_remat_ver == 4 && g_remat_w8) launch(k_bwd_remat3<true, false, 8>, R3_LDS, 768);
-    else if (g_remat_ver == 4) launch(k_bwd_remat3<true>, R3_LDS);
-    else launch(k_bwd_remat3<false>, R3_LDS);
+    if (last) launch(k_bwd_remat3<true, true, 4>, R3L_LDS);
+    else launch(k_bwd_remat3<true, false, 4>, R3_LDS);
   }
-  // g_0's partial sets: one per pair from the fused layer-1 launch, else one per workgroup of k_wgrad_enc
-  const int ne = fuse0 ? FB_PAIRS : (int)std::min<int64_t>(ntiles, 2 * FB_PAIRS);
-  if (!fuse0) {
-    // 2 x 256 x 64 fp32-FLOP per sample; 1 KiB of g + 256 B of encoding in
-    ProfScope ps(s, PT_BWD_WGRAD_H, 2.0 * 256.0 * 64 * dn, (1024.0 + 256.0) * dn);
-    hipLaunchKernelGGL(k_wgrad_enc, dim3(2 * FB_PAIRS), dim3(512), WE_LDS, s, (const char*)S[1], (const char*)nullptr,
-                       (const char*)encimg, n, (const int*)ws.gexp, (const unsigned*)ws.pbound, part_e0,
-                       (float*)nullptr);
-  }
-  ProfScope ps(s, PT_BWD_MISC, 0.0, (double)FB_PAIRS * GD_PART * 4.0 + ne * WgradCfg<1>::PART * 4.0);
+  // layer 1's G_d partials and g_0's partial sets (one per pair, from layer 1's launch)
+  ProfScope ps(s, PT_BWD_MISC, 0.0, (double)FB_PAIRS * GD_PART * 4.0 + FB_PAIRS * WgradCfg<1>::PART * 4.0);
   hipLaunchKernelGGL(k_gd_tail, dim3(256, 2), dim3(1024), 0, s, (const float*)pset[1], ws.gd + GD_LAYER,
-                     (const float*)part_e0, ws.gacc + G.w[0], ws.gacc + G.b[0], ne);
+                     (const float*)part_e0, ws.gacc + G.w[0], ws.gacc + G.b[0], FB_PAIRS);
   GdProj gp;
   for (int L = 0; L < 8; ++L) gp.dW[L] = ws.gacc + G.w[L];
   gp.coef = ws.coef;
@@ -5417,10 +5121,11 @@ static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdW
 }
 
 // One chunk through the rematerialised backward (no activation store): max |dL/dlogit|, k_fb_prep on the fold's
-// statistics, the chunk's encoding image, g_7 (k_g7), layers 7..1 each in ONE k_bwd_remat2 launch, the encoding
-// columns of layers 0 and 4 (k_wgrad_enc on the pre-split g_0 and g_4 and the encoding image), the last partial sums.
+// statistics, the chunk's encoding image, g_7 (k_g7), then the layers: remat3_layers (the default), or under remat
+// version 2 layers 7..1 each in ONE k_bwd_remat2 launch, the encoding columns of layers 0 and 4 (k_wgrad_enc on the
+// pre-split g_0 and g_4 and the encoding image) and the last partial sums.
 // g buffers, all pre-split: S0 / S1 alternate (g_7, g_5, g_3, g_1 in S0; g_6, g_2, g_0 in S1), g_4 in S2 (kept to
-// the end for k_wgrad_enc).
+// the end for k_wgrad_enc; the default keeps g_0 in LDS).
 static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
                         const f16x8* pimg, const float* pscl, int64_t ci, int64_t c0, int64_t n, const float* rays,
                         int ray_stride, const float* z, int n_samples, float eps, const float* grad, hipStream_t s,
@@ -5431,14 +5136,10 @@ static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs&
                                 (int)RB_LDS));
     PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat2<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)RB_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)R3_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)R3_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)R3L_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, false, 8>,
+    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, false, 4>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3_LDS));
+    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, true, 4>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3L_LDS));
     PCN_HIP(hipFuncSetAttribute((const void*)k_g7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G7_LDS));
     PCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_enc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WE_LDS));
     pcn_attr_done(attr);
@@ -5485,8 +5186,8 @@ static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs&
   }
   const unsigned fbg = (unsigned)(2 * FB_PAIRS);
   float* const pset[2] = {ws.part, ws.part + (size_t)FB_PAIRS * WgradCfg<2>::PART};
-  if (g_remat_ver >= 3) {
-    remat3_layers(P, G, ws, FB, pimg, pscl, ci, n, grad, s, encimg, prow, psrow, S, S2, pset);
+  if (g_remat_ver == 4) {
+    remat3_layers(P, G, ws, FB, ci, n, s, encimg, prow, psrow, S, S2, pset);
     return;
   }
   for (int L = 7; L >= 1; --L) {

@@ -123,9 +123,9 @@ _TRAIN_FUSED = True   # the library's own default is mode 1 (f16x2_3)
 
 
 def set_remat_version(version: int) -> int:
-    """Select the default training backward's layer kernel (4: k_bwd_remat3 with the BatchNorm-backward epilogue on
-    the W waves, the default; 3: k_bwd_remat3 with it on the D waves; 2: k_bwd_remat2); returns the previous one
-    (pcnerf_set_remat_version)."""
+    """Select the default training backward's layer kernel (pcnerf_set_remat_version): 4, k_bwd_remat3 with the
+    BatchNorm-backward epilogue on the W waves, the default; 2, k_bwd_remat2 (for A/B).  Returns the previous one.
+    Anything else (3, the retired D-wave-epilogue form, included) raises RuntimeError and changes nothing."""
     prev = H.lib().pcnerf_set_remat_version(int(version))
     if prev < 0:
         raise RuntimeError(H.lib().pcnerf_last_error().decode())
@@ -136,6 +136,10 @@ def get_remat_version() -> int:
     v = set_remat_version(4)
     set_remat_version(v)
     return v
+
+
+if os.environ.get("PCNERF_REMAT_VER"):   # (3, once an A/B switch, stops the import instead of being ignored)
+    set_remat_version(int(os.environ["PCNERF_REMAT_VER"]))
 
 
 def set_composite_group(group: int) -> int:
