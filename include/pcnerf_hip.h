@@ -332,6 +332,25 @@ int pcnerf_composite_backward(const float* p, const float* z, int64_t n_rays, in
                               const float* grad_depth, const float* grad_free_loss, const float* grad_depth_loss,
                               void* workspace, float* grad_logit, void* stream);
 
+/* ---------------------------------------------------------------- eval-mode gradients to the sample geometry
+ * The eval network is p = sigmoid(a . Embedding(x) + c) with (a, c) = `fold`, the 64 doubles of pcnerf_nof_fold_eval
+ * (SURVEY fact 1), so d logit / d x = J(x)^T a with J = d Embedding / d x (models.py:27-41: the identity columns,
+ * d sin(2^k x_m) = 2^k cos(2^k x_m), d cos(2^k x_m) = -2^k sin(2^k x_m)) -- exactly, whichever eval math computed p.
+ * grad_logit is pcnerf_composite_backward's output.  The encoding is recomputed at the float32 position the forward
+ * evaluated; the dots and the per-ray sums accumulate in float64 and round once; no atomics (bit-reproducible).
+ * pcnerf_nof_points_eval_backward: grad_pts[g, 0:3] = grad_logit[g] * J(pts[g])^T a for pts (n, 3) taken verbatim --
+ *   what autograd of inference_val's chunk loop (render.py:18-25) leaves in samples_xy.grad.  n == 0 succeeds without
+ *   a launch (no pointer is then read: all may be NULL).
+ * pcnerf_nof_query_eval_backward: with x_s = fl(o + fl(d * z[r, s])) (o = rays[r, 0:3], d = rays[r, 3:6], render.py:
+ *   518-520 / :458) and g_s = grad_logit[r, s] * J(x_s)^T a, grad_rays6[r, 0:3] = sum_s g_s and grad_rays6[r, 3:6] =
+ *   sum_s z[r, s] g_s -- what autograd of render_rays_val's eval pass (render.py:485-536) leaves in rays.grad[:, 0:6];
+ *   z is a constant of the pass.  grad_rays6 is (n_rays, 6), contiguous.  ray_stride >= 6, n_samples >= 1;
+ *   n_rays == 0 succeeds without a launch.  No argument is nullable otherwise. */
+int pcnerf_nof_points_eval_backward(const float* pts, int64_t n, const double* fold, const float* grad_logit,
+                                    float* grad_pts, void* stream);
+int pcnerf_nof_query_eval_backward(const float* rays, int64_t n_rays, int ray_stride, const float* z, int n_samples,
+                                   const double* fold, const float* grad_logit, float* grad_rays6, void* stream);
+
 /* ---------------------------------------------------------------- importance resampling
  * z_fine[ray, :] = sort(cat(z, sample_pdf(mid(z), weights[:, 1:-1], n_importance, det = (u == NULL))))
  * (render.py:371-412, :463-467).  `u` [n_rays, n_importance] replaces torch.rand when not NULL. */

@@ -10,8 +10,12 @@ torch.autograd.Functions, each owning one forward kernel chain and its hand-writ
     point-sourced fused query and its rematerialised backward (pcnerf_nof_points_train_fused_state /
     pcnerf_nof_points_train_backward_remat).  TrainPass's behaviour and saved tensors are untouched by it.
   * NofForward -- NOF.forward on an embedded batch in train mode (models.py:183-203).
-Gradients flow to the 34 trainable tensors of the network; inputs (rays, positions) get none, as in the
-reference where they never require grad.
+  * EvalPass / EvalPassPoints -- one eval-mode pass of render_rays_val / inference_val (render.py:485-536, :13-36) on
+    a FROZEN network, with the gradient of depth to rays[:, 0:6] / to samples_xy: backward =
+    pcnerf_composite_backward -> pcnerf_nof_query_eval_backward / pcnerf_nof_points_eval_backward.
+In the train-mode Functions gradients flow to the 34 trainable tensors of the network and the inputs (rays, positions)
+get none, as in the reference's training step where they never require grad; in the eval-mode ones the geometry gets
+the gradient and the parameters none.
 """
 from __future__ import annotations
 
@@ -104,6 +108,69 @@ class TrainPassPoints(torch.autograd.Function):
         grads = _ops.nof_points_backward_remat(ctx.model, pts, ctx.chunk, g_logit, ctx.state)
         ctx.state = None
         return (None,) * 10 + tuple(grads)
+
+
+def _eval_fold(model) -> torch.Tensor:
+    """(a, c) of the frozen eval network (pcnerf::fold_eval): d logit / d encoding is the constant a."""
+    from . import _torch_ops
+    _ops._bn_config(model)
+    return torch.ops.pcnerf.fold_eval([t.detach() for t in _torch_ops.eval_params(model)])
+
+
+class EvalPass(torch.autograd.Function):
+    """One eval-mode pass of render_rays_val (render.py:512-533) with the gradient of depth to the ray origins and
+    directions: forward = the renderer's own eval query (``query``, whatever eval path is selected) + compositing,
+    the calls and so the bits of the forward-only render; backward = pcnerf_composite_backward (dL/dlogit from
+    dL/ddepth) -> pcnerf_nof_query_eval_backward.  The eval network is sigmoid(a . e + c), so its
+    Jacobian to the encoding is the fold vector a whichever eval math computed p; it is composed once per pass and
+    saved.  z is a constant of the pass; the parameters are frozen (no gradient to them); weights are
+    non-differentiable (the compositing backward takes grad_depth only)."""
+
+    @staticmethod
+    def forward(ctx, query, model, rays, z, noise, noise_std, eps, chunk, want_weights):
+        p = query(model, rays, z, chunk)
+        w, depth, _, _ = torch.ops.pcnerf.composite(p, z, noise, noise_std, eps, None, 10, 11, 14, want_weights)
+        ctx.noise_std, ctx.eps = noise_std, eps
+        ctx.save_for_backward(rays, z, p, noise, _eval_fold(model))
+        ctx.mark_non_differentiable(w)
+        return w, depth
+
+    @staticmethod
+    def backward(ctx, g_w, g_depth):
+        rays, z, p, noise, fold = ctx.saved_tensors
+        g_logit = _ops.composite_backward(p, z, noise, ctx.noise_std, ctx.eps, None, 0, g_depth, None, None)
+        g_rays = torch.zeros_like(rays)   # every column but the origin and the direction: zero
+        g_rays[:, :6] = torch.ops.pcnerf.rays_grad_eval(rays, z, g_logit, fold)
+        return (None, None, g_rays) + (None,) * 6
+
+
+class EvalPassPoints(torch.autograd.Function):
+    """EvalPass on explicit sample positions (inference_val, render.py:13-36): ``pts`` (R * S, 3) are the
+    materialised samples, read verbatim; the gradient of depth goes to them (pcnerf_nof_points_eval_backward)."""
+
+    @staticmethod
+    def forward(ctx, query_points, model, pts, z, noise, noise_std, eps, chunk):
+        p = query_points(model, pts, z.shape[0], z.shape[1], chunk)
+        w, depth, _, _ = torch.ops.pcnerf.composite(p, z, noise, noise_std, eps, None, 10, 11, 14, True)
+        ctx.noise_std, ctx.eps = noise_std, eps
+        ctx.save_for_backward(pts, z, p, noise, _eval_fold(model))
+        ctx.mark_non_differentiable(w)
+        return w, depth
+
+    @staticmethod
+    def backward(ctx, g_w, g_depth):
+        pts, z, p, noise, fold = ctx.saved_tensors
+        g_logit = _ops.composite_backward(p, z, noise, ctx.noise_std, ctx.eps, None, 0, g_depth, None, None)
+        return (None, None, torch.ops.pcnerf.points_grad_eval(pts, g_logit.view(-1), fold)) + (None,) * 5
+
+
+def check_frozen_eval(model, what: str) -> None:
+    """The geometry gradient exists for the frozen eval network only: train-mode BatchNorm takes its statistics from
+    the batch, which couples every sample's output to every other sample's position."""
+    if model.training:
+        raise NotImplementedError(f"no gradient flows to {what} through a train-mode module: BatchNorm batch "
+                                  "statistics couple the samples; call model.eval() (frozen parameters) or detach "
+                                  f"{what}")
 
 
 class NofForward(torch.autograd.Function):

@@ -143,6 +143,8 @@ _SIGS = {
     "pcnerf_composite_backward_workspace_bytes": (c_size, [c_int]),
     "pcnerf_composite_backward": (c_int, [vp, vp, i64, c_int, vp, c_float, c_float, vp, c_int, c_int, c_int, c_int,
                                           c_int, c_int, vp, vp, vp, vp, vp, vp]),
+    "pcnerf_nof_points_eval_backward": (c_int, [vp, i64, vp, vp, vp, vp]),
+    "pcnerf_nof_query_eval_backward": (c_int, [vp, i64, c_int, vp, c_int, vp, vp, vp, vp]),
 }
 
 

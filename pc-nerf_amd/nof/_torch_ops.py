@@ -138,25 +138,31 @@ def _check_query(rays: Tensor, z: Tensor, packed: Tensor) -> None:
         raise RuntimeError("pcnerf::query_eval: rays, z and packed must be on one device")
 
 
-@torch.library.custom_op(f"{NS}::pack_eval", mutates_args=())
-def pack_eval(params: list[Tensor]) -> Tensor:
-    """The eval network image (BatchNorm folded, MFMA operand order) from the module's 50 tensors in
-    pcnerf_nof_params order: lin_w[8], lin_b[8], bn_w[8], bn_b[8], bn_rm[8], bn_rv[8], out_w, out_b."""
+def _params_struct(op: str, params: list) -> "H.NofParams":
+    """The 50 tensors of pcnerf_nof_params order, checked against the module's layout, as the C struct."""
     if len(params) != 50:
-        raise RuntimeError(f"pcnerf::pack_eval takes 50 parameter tensors, got {len(params)}")
+        raise RuntimeError(f"pcnerf::{op} takes 50 parameter tensors, got {len(params)}")
     s = H.NofParams()
     for i, (t, shp) in enumerate(zip(params, _param_shapes())):
         H.require_device(t)
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError("NOF parameters must be contiguous float32 device tensors")
         if tuple(t.shape) != shp:
-            raise RuntimeError(f"pcnerf::pack_eval: parameter {i} has shape {tuple(t.shape)}, expected {shp} "
+            raise RuntimeError(f"pcnerf::{op}: parameter {i} has shape {tuple(t.shape)}, expected {shp} "
                                "(NOF(feature_size=256, in_channels_xy=63, use_skip=True))")
     for i in range(8):
         s.lin_w[i], s.lin_b[i] = params[i].data_ptr(), params[8 + i].data_ptr()
         s.bn_w[i], s.bn_b[i] = params[16 + i].data_ptr(), params[24 + i].data_ptr()
         s.bn_rm[i], s.bn_rv[i] = params[32 + i].data_ptr(), params[40 + i].data_ptr()
     s.out_w, s.out_b = params[48].data_ptr(), params[49].data_ptr()
+    return s
+
+
+@torch.library.custom_op(f"{NS}::pack_eval", mutates_args=())
+def pack_eval(params: list[Tensor]) -> Tensor:
+    """The eval network image (BatchNorm folded, MFMA operand order) from the module's 50 tensors in
+    pcnerf_nof_params order: lin_w[8], lin_b[8], bn_w[8], bn_b[8], bn_rm[8], bn_rv[8], out_w, out_b."""
+    s = _params_struct("pack_eval", params)
     import ctypes
     out = torch.empty(_packed_floats(), dtype=torch.float32, device=params[0].device)
     H.check(H.lib().pcnerf_nof_pack_eval(ctypes.byref(s), out.data_ptr(), H.stream_of(out)))
@@ -221,6 +227,78 @@ def query_points_eval(pts: Tensor, packed: Tensor) -> Tensor:
 @query_points_eval.register_fake
 def _(pts, packed):
     return pts.new_empty(tuple(pts.shape[:-1]), dtype=torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------- eval gradients
+# The eval network is sigmoid(a . Embedding(x) + c), so the logit's gradient to a position is
+# J(x)^T a with the constant a of pcnerf::fold_eval -- whichever eval math computed p.  These are the backward
+# kernels of nof._autograd.EvalPass / EvalPassPoints; they are plain operators (no autograd formula of their own).
+@torch.library.custom_op(f"{NS}::fold_eval", mutates_args=())
+def fold_eval(params: list[Tensor]) -> Tensor:
+    """(a, c) of the eval network, 64 float64 (a = fold[:63], c = fold[63]), composed in float64 from the module's 50
+    tensors in pcnerf::pack_eval's order (pcnerf_nof_fold_eval)."""
+    s = _params_struct("fold_eval", params)
+    import ctypes
+    out = torch.empty(64, dtype=torch.float64, device=params[0].device)
+    H.check(H.lib().pcnerf_nof_fold_eval(ctypes.byref(s), out.data_ptr(), H.stream_of(out)))
+    return out
+
+
+@fold_eval.register_fake
+def _(params):
+    return params[0].new_empty((64,), dtype=torch.float64)
+
+
+def _one_device(op: str, *ts: Tensor) -> None:
+    if any(t.device != ts[0].device for t in ts):
+        raise RuntimeError(f"pcnerf::{op}: all operands must be on one device")
+
+
+@torch.library.custom_op(f"{NS}::points_grad_eval", mutates_args=())
+def points_grad_eval(pts: Tensor, grad_logit: Tensor, fold: Tensor) -> Tensor:
+    """d/d pts of the eval query of explicit positions (autograd of render.py:18-25 to samples_xy): pts (N, 3) or
+    (R, S, 3), grad_logit (N,) or (R, S) = dL/dlogit per sample, fold = pcnerf::fold_eval -> pts' shape."""
+    op = "points_grad_eval"
+    H.require_device(pts)
+    if pts.dim() not in (2, 3) or pts.shape[-1] != 3:
+        raise RuntimeError(f"pcnerf::{op}: pts has shape {tuple(pts.shape)}, expected (N, 3) or (R, S, 3)")
+    _need(op, "pts", pts, tuple(pts.shape))
+    _need(op, "grad_logit", grad_logit, tuple(pts.shape[:-1]))
+    _need(op, "fold", fold, (64,), torch.float64)
+    _one_device(op, pts, grad_logit, fold)
+    out = torch.empty_like(pts)
+    H.check(H.lib().pcnerf_nof_points_eval_backward(pts.data_ptr(), grad_logit.numel(), fold.data_ptr(),
+                                                    grad_logit.data_ptr(), out.data_ptr(), H.stream_of(pts)))
+    return out
+
+
+@points_grad_eval.register_fake
+def _(pts, grad_logit, fold):
+    return torch.empty_like(pts, dtype=torch.float32)
+
+
+@torch.library.custom_op(f"{NS}::rays_grad_eval", mutates_args=())
+def rays_grad_eval(rays: Tensor, z: Tensor, grad_logit: Tensor, fold: Tensor) -> Tensor:
+    """d/d rays[:, 0:6] of the eval query of o + d z (autograd of render.py:518-520 + :18-25 to the origins and
+    directions, z constant): rays (R, >=6), z (R, S), grad_logit (R, S), fold = pcnerf::fold_eval -> (R, 6), columns
+    0:3 sum_s g_s, 3:6 sum_s z_s g_s."""
+    op = "rays_grad_eval"
+    _need(op, "z", z, (None, ("min", 1)))
+    _need(op, "rays", rays, (z.shape[0], ("min", 6)))
+    _need(op, "grad_logit", grad_logit, tuple(z.shape))
+    _need(op, "fold", fold, (64,), torch.float64)
+    _one_device(op, rays, z, grad_logit, fold)
+    R, S = z.shape
+    out = torch.empty((R, 6), dtype=torch.float32, device=z.device)
+    H.check(H.lib().pcnerf_nof_query_eval_backward(rays.data_ptr(), R, rays.shape[1], z.data_ptr(), S,
+                                                   fold.data_ptr(), grad_logit.data_ptr(), out.data_ptr(),
+                                                   H.stream_of(z)))
+    return out
+
+
+@rays_grad_eval.register_fake
+def _(rays, z, grad_logit, fold):
+    return z.new_empty((z.shape[0], 6), dtype=torch.float32)
 
 
 # ----------------------------------------------------------------------------------------------- compositing
@@ -350,4 +428,4 @@ def op_names() -> list:
     """The registered operator names (tests)."""
     return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "query_points_eval", "composite",
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
-            "pointwise_loss_backward"]
+            "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval"]

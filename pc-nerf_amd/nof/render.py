@@ -20,7 +20,14 @@ Differences from the reference, all deliberate:
   * gradients: ``render_rays_train`` is differentiable (train-mode networks): with autograd enabled and
     parameters requiring grad, each pass runs as ``nof._autograd.TrainPass`` whose backward is the HIP
     compositing backward + the NOF backward (chunks recomputed), so ``loss.backward()`` of train_kitti.py:155
-    fills ``.grad`` of both networks.  The inference renderers stay forward-only (they raise under autograd).
+    fills ``.grad`` of both networks.  ``render_rays_val`` and ``inference_val`` are differentiable with respect
+    to their GEOMETRY on frozen eval-mode networks: when ``rays`` / ``samples_xy`` requires grad, each pass runs as
+    ``nof._autograd.EvalPass`` / ``EvalPassPoints``, whose backward is the HIP compositing backward + the eval
+    network's position gradient (pcnerf_nof_query_eval_backward / pcnerf_nof_points_eval_backward), so
+    ``depth.backward()`` reaches ``rays[:, 0:6]`` / ``samples_xy`` as it does through the reference's eager eval
+    render.  Sample depths are constants there.  The other renderers (``render_rays``, ``inference``,
+    ``inference_0525_2``, the two-step view render) stay forward-only: their peak selection and ``depth2`` are not
+    differentiable in any useful sense; parameters that require grad raise in every eval renderer.
 """
 from __future__ import annotations
 
@@ -128,8 +135,10 @@ def _query_points(model, pts, R, S, chunk):
     return _ops.query_points(model, pts, R, S, chunk)
 
 
-def _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child=None, differentiable=False):
-    """_check_inputs for the inference_* helpers -> (pts (R * S, 3), z (R, S)) contiguous float32."""
+def _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child=None, differentiable=False,
+                         points_grad=False):
+    """_check_inputs for the inference_* helpers -> (pts (R * S, 3), z (R, S)) contiguous float32.  ``points_grad``
+    (inference_val): samples_xy may require grad; under autograd pts then stays attached to it."""
     for name, t in (("samples_xy", samples_xy), ("z_vals", z_vals), ("near_far_child", near_far_child)):
         if t is not None and not (torch.is_tensor(t) and t.is_cuda):
             raise RuntimeError(f"nof.render (HIP) takes device-resident tensors; move {name} with .to('cuda') -- "
@@ -149,8 +158,15 @@ def _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child
         if not differentiable:
             raise NotImplementedError("this HIP inference helper is forward-only; call it under torch.no_grad()")
         _autograd.check_trainable(model)
-    if samples_xy.requires_grad:
-        raise NotImplementedError("no gradient flows to samples_xy through the HIP query; detach it")
+    if samples_xy.requires_grad and not points_grad:
+        raise NotImplementedError("no gradient flows to samples_xy through this HIP helper (inference_val alone "
+                                  "differentiates its positions, on a frozen eval-mode module); detach it")
+    if points_grad and torch.is_grad_enabled() and samples_xy.requires_grad:
+        if z_vals.requires_grad:
+            raise NotImplementedError("z_vals is a constant of the HIP eval render: no gradient flows to it; "
+                                      "detach it (the gradient goes to samples_xy)")
+        _autograd.check_frozen_eval(model, "samples_xy")
+        return samples_xy.float().contiguous().view(-1, 3), z_vals.detach().float().contiguous()
     return samples_xy.detach().float().contiguous().view(-1, 3), z_vals.detach().float().contiguous()
 
 
@@ -160,8 +176,19 @@ def inference_val(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tensor,
                   isval=False, sub_nerf_test_num=4, *, rng=None):
     """render.py:13-36 -> (depth_final (R,), weights_origin (R, S)).  ``rays``, ``near_far_point``,
     ``range_readings``, ``ray_class``, ``isval`` and ``sub_nerf_test_num`` are accepted and unused, as in the
-    reference.  ``rng["noise"]`` (R, S) injects the randn draw (taken only when noise_std != 0)."""
-    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child)
+    reference.  ``rng["noise"]`` (R, S) injects the randn draw (taken only when noise_std != 0).
+
+    Differentiable with respect to ``samples_xy`` when it requires grad, on a frozen eval-mode module
+    (``depth_final.backward()`` fills ``samples_xy.grad`` as the reference's eager render does): the pass runs as
+    nof._autograd.EvalPassPoints.  ``weights_origin`` carries no gradient, ``z_vals`` is a constant (it raises if it
+    requires grad), a train-mode module raises (batch statistics couple the samples) and parameters that require
+    grad raise as before.  Without a tensor requiring grad the calls, and the outputs' bits, are the forward-only
+    ones."""
+    pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child, points_grad=True)
+    if pts.requires_grad:
+        w, depth = _autograd.EvalPassPoints.apply(_query_points, model, pts, z, _noise(rng, "noise", z, noise_std),
+                                                  float(noise_std), float(epsilon), int(chunk))
+        return depth, w
     p = _query_points(model, pts, z.shape[0], z.shape[1], chunk)
     w, depth, _, _ = P.composite(p, z, _noise(rng, "noise", z, noise_std), float(noise_std), float(epsilon), None,
                                  10, 11, 14, True)
@@ -293,9 +320,29 @@ def render_rays_train(model: NOF, model_fine: NOF, embedding_xy: Embedding, rays
 def render_rays_val(model: NOF, model_fine: NOF, embedding_xy: Embedding, rays: torch.Tensor, sub_nerf_test_num=4,
                     N_samples=64, N_importance=128, use_disp=False, perturb=0, noise_std=1, chunk=1024 * 3,
                     isval=False, *, rng=None):
-    """render.py:485-536 -> {'depth_fine', 'depth'}."""
+    """render.py:485-536 -> {'depth_fine', 'depth'}.
+
+    Differentiable with respect to the ray geometry when ``rays`` requires grad, on frozen eval-mode networks: both
+    passes run as nof._autograd.EvalPass and the gradients of ``depth`` and of ``depth_fine`` reach ``rays[:, 0:3]``
+    (origins) and ``rays[:, 3:6]`` (directions); every other column's gradient is zero.  Sample depths are constants
+    of the render: the coarse z comes from the near / far columns of the detached rays, and the fine z is detached
+    from the coarse weights, as the reference detaches it (render.py:523).  A train-mode module raises (batch
+    statistics couple the samples); parameters that require grad raise as before.  Without a tensor requiring grad
+    the calls, and the outputs' bits, are the forward-only ones."""
     rays = _check_inputs(model, model_fine, embedding_xy, rays, 8)
     R = rays.shape[0]
+    if torch.is_grad_enabled() and rays.requires_grad:
+        for m in (model, model_fine):
+            _autograd.check_frozen_eval(m, "rays")
+        rd = rays.detach()
+        z = _coarse(rd, N_samples, False, 0.0, perturb, rng)
+        w, depth = _autograd.EvalPass.apply(_query, model, rays, z, _noise(rng, "noise", z, noise_std),
+                                            float(noise_std), EPSILON, int(chunk), True)
+        u = None if perturb == 0 else _draw(rng, "u", (R, N_importance), rays.device, torch.rand)
+        zf = P.resample(z, w, int(N_importance), u)
+        _, depth_f = _autograd.EvalPass.apply(_query, model_fine, rays, zf, _noise(rng, "noise_fine", zf, noise_std),
+                                              float(noise_std), EPSILON, int(chunk), False)
+        return {"depth_fine": depth_f, 'depth': depth}
     z = _coarse(rays, N_samples, False, 0.0, perturb, rng)
     p = _query(model, rays, z, chunk)
     w, depth, _, _ = P.composite(p, z, _noise(rng, "noise", z, noise_std), float(noise_std), EPSILON, None, 10, 11,
