@@ -351,6 +351,47 @@ int pcnerf_nof_points_eval_backward(const float* pts, int64_t n, const double* f
 int pcnerf_nof_query_eval_backward(const float* rays, int64_t n_rays, int ray_stride, const float* z, int n_samples,
                                    const double* fold, const float* grad_logit, float* grad_rays6, void* stream);
 
+/* ---------------------------------------------------------------- eval-mode gradients to the parameters
+ * Frozen-BatchNorm training: what autograd leaves in the 34 parameters' .grad through render.py:38-163 / :13-36 and
+ * models.py:103-123 with the module in eval mode (running statistics used, not updated).  The eval network is
+ * logit = a(theta) . Embedding(x) + c(theta), so with g_s = dL/dlogit of sample s the parameter
+ * gradients of a whole pass are those of ONE pseudo-sample: dL/dtheta = d/dtheta [a(theta) . m + c(theta) s0] with
+ * m = sum_s g_s Embedding(x_s) (63 numbers) and s0 = sum_s g_s.  Two stages:
+ *   moments  mom[0..62] = m, mom[63] = s0 in float64 (device, 64 doubles), the encoding recomputed with the forward's
+ *            own arithmetic at the float32 position it evaluated, every term g_s e_s formed exactly in float64;
+ *            per-workgroup partials in `workspace` summed in a fixed order, no atomics, launch geometry a function of
+ *            the sample count alone (two runs give equal bits).  `workspace` takes
+ *            pcnerf_nof_eval_pgrad_workspace_bytes(total samples) bytes, 8-byte aligned.
+ *            _rays: x_s = fl(o + fl(d z[r, s])) (render.py:44-45 / :458); _points: pts (n, 3) verbatim;
+ *            _embedded: emb (n, 63) given; p != NULL takes `grad` as dL/dp and forms dL/dlogit = grad p (1 - p).
+ *   algebra  pcnerf_nof_eval_param_grads: the pseudo-sample's forward and backward through the 9 layers in float64;
+ *            fl32(value) is ADDED to every non-NULL buffer of `grads` (a NULL one is skipped); the Linear-bias and
+ *            BatchNorm-shift gradients are NOT zero here (no batch mean is removed).  bn_rm / bn_rv are read only.
+ * The _param_backward entries run both stages (mom at the head of `workspace`); grad_logit is
+ * pcnerf_composite_backward's output; pcnerf_nof_forward_eval_param_backward takes p = NOF.forward(emb)'s output and
+ * grad_p = dL/dp.  Zero samples succeed without a launch (nothing is added, mom is not written); null or
+ * short-workspace arguments are refused before any launch. */
+size_t pcnerf_nof_eval_pgrad_workspace_bytes(int64_t total_samples);
+int pcnerf_nof_eval_gmoments_rays(const float* rays, int64_t n_rays, int ray_stride, const float* z, int n_samples,
+                                  const float* grad_logit, void* workspace, size_t workspace_bytes, double* mom,
+                                  void* stream);
+int pcnerf_nof_eval_gmoments_points(const float* pts, int64_t n, const float* grad_logit, void* workspace,
+                                    size_t workspace_bytes, double* mom, void* stream);
+int pcnerf_nof_eval_gmoments_embedded(const float* emb, int64_t n, const float* p, const float* grad, void* workspace,
+                                      size_t workspace_bytes, double* mom, void* stream);
+int pcnerf_nof_eval_param_grads(const pcnerf_nof_params* params, float eps, const double* mom,
+                                const pcnerf_nof_grads* grads, void* stream);
+int pcnerf_nof_query_eval_param_backward(const float* rays, int64_t n_rays, int ray_stride, const float* z,
+                                         int n_samples, const pcnerf_nof_params* params, float eps,
+                                         const float* grad_logit, void* workspace, size_t workspace_bytes,
+                                         const pcnerf_nof_grads* grads, void* stream);
+int pcnerf_nof_points_eval_param_backward(const float* pts, int64_t n, const pcnerf_nof_params* params, float eps,
+                                          const float* grad_logit, void* workspace, size_t workspace_bytes,
+                                          const pcnerf_nof_grads* grads, void* stream);
+int pcnerf_nof_forward_eval_param_backward(const float* emb, int64_t n, const pcnerf_nof_params* params, float eps,
+                                           const float* p, const float* grad_p, void* workspace,
+                                           size_t workspace_bytes, const pcnerf_nof_grads* grads, void* stream);
+
 /* ---------------------------------------------------------------- importance resampling
  * z_fine[ray, :] = sort(cat(z, sample_pdf(mid(z), weights[:, 1:-1], n_importance, det = (u == NULL))))
  * (render.py:371-412, :463-467).  `u` [n_rays, n_importance] replaces torch.rand when not NULL. */

@@ -9,13 +9,20 @@ torch.autograd.Functions, each owning one forward kernel chain and its hand-writ
   * TrainPassPoints -- the same pass on materialised sample positions (inference_train, render.py:38-163): the
     point-sourced fused query and its rematerialised backward (pcnerf_nof_points_train_fused_state /
     pcnerf_nof_points_train_backward_remat).  TrainPass's behaviour and saved tensors are untouched by it.
-  * NofForward -- NOF.forward on an embedded batch in train mode (models.py:183-203).
+  * NofForward -- NOF.forward on an embedded batch (models.py:183-203): train mode, or eval mode with the frozen
+    running statistics (pcnerf_nof_forward_eval_param_backward).
+  * FrozenPass / FrozenPassPoints -- TrainPass / TrainPassPoints for an EVAL-mode module whose parameters require
+    grad (frozen-BatchNorm training: model.eval() keeps the running statistics, every weight trains).  The eval
+    network is a(theta) . e + c(theta), so the parameter gradients of a pass are those of one float64 pseudo-sample
+    with input sum_s g_s e_s: backward = pcnerf_composite_backward -> pcnerf::eval_gmoments_* ->
+    pcnerf::eval_param_grads.  No activations, state or rematerialisation; running statistics and
+    num_batches_tracked are not touched; the Linear-bias and BatchNorm-shift gradients are not zero here.
   * EvalPass / EvalPassPoints -- one eval-mode pass of render_rays_val / inference_val (render.py:485-536, :13-36) on
     a FROZEN network, with the gradient of depth to rays[:, 0:6] / to samples_xy: backward =
     pcnerf_composite_backward -> pcnerf_nof_query_eval_backward / pcnerf_nof_points_eval_backward.
-In the train-mode Functions gradients flow to the 34 trainable tensors of the network and the inputs (rays, positions)
-get none, as in the reference's training step where they never require grad; in the eval-mode ones the geometry gets
-the gradient and the parameters none.
+In the train-mode and the Frozen* Functions gradients flow to the 34 trainable tensors of the network and the inputs
+(rays, positions) get none, as in the reference's training step where they never require grad; in EvalPass /
+EvalPassPoints the geometry gets the gradient and the parameters none.
 """
 from __future__ import annotations
 
@@ -164,6 +171,80 @@ class EvalPassPoints(torch.autograd.Function):
         return (None, None, torch.ops.pcnerf.points_grad_eval(pts, g_logit.view(-1), fold)) + (None,) * 5
 
 
+def _frozen_param_grads(model, mom) -> tuple:
+    """pcnerf::eval_param_grads on the module's tensors: the 34 gradients in grad_params order."""
+    from . import _torch_ops
+    _, bn_eps = _ops._bn_config(model)
+    return tuple(torch.ops.pcnerf.eval_param_grads([t.detach() for t in _torch_ops.eval_params(model)], mom, bn_eps))
+
+
+class FrozenPass(torch.autograd.Function):
+    """One pass of render_rays_train (render.py:38-163, 416-482) on an EVAL-mode module whose parameters require grad
+    (frozen BatchNorm: the running statistics normalise and are not touched).  forward = the renderer's own eval
+    query (``query``, whatever eval path is selected) + compositing + child losses, the calls and so the bits of the
+    no-grad render.  backward = pcnerf_composite_backward (dL/dlogit) -> pcnerf::eval_gmoments_rays (the pass's
+    moments sum_s g_s e_s, sum_s g_s) -> pcnerf::eval_param_grads (one float64 pseudo-sample): the eval network is
+    a(theta) . e + c(theta), so no activation, state or rematerialisation is needed -- it saves what
+    TrainPass saves, minus the state.  Outputs as TrainPass; the rays get no gradient."""
+
+    @staticmethod
+    def forward(ctx, query, model, rays, z, noise, noise_std, eps, chunk, with_losses, divide, sub_num, *params):
+        P = torch.ops.pcnerf
+        p = query(model, rays, z, chunk)
+        w, depth, fr, sl = P.composite(p, z, noise, noise_std, eps, rays if with_losses else None, 10, 11, 14, True)
+        if with_losses:
+            free, dl = P.child_losses(fr, sl, rays, divide, sub_num)
+        else:
+            free = dl = torch.zeros((), dtype=torch.float32, device=z.device)
+        ctx.model, ctx.noise_std, ctx.eps = model, noise_std, eps
+        ctx.with_losses, ctx.sub = with_losses, (sub_num if divide else 0)
+        ctx.save_for_backward(rays, z, p, noise)
+        ctx.mark_non_differentiable(w)
+        return w, depth, free, dl
+
+    @staticmethod
+    def backward(ctx, g_w, g_depth, g_free, g_dl):
+        rays, z, p, noise = ctx.saved_tensors
+        if not ctx.with_losses:
+            g_free = g_dl = None
+        g_logit = _ops.composite_backward(p, z, noise, ctx.noise_std, ctx.eps, rays if ctx.with_losses else None,
+                                          ctx.sub, g_depth, g_free, g_dl)
+        mom = torch.ops.pcnerf.eval_gmoments_rays(rays, z, g_logit)
+        return (None,) * 11 + _frozen_param_grads(ctx.model, mom)
+
+
+class FrozenPassPoints(torch.autograd.Function):
+    """FrozenPass on explicit sample positions (inference_train, render.py:38-163): ``pts`` (R * S, 3) read verbatim,
+    ``table`` the per-ray scalars of TrainPassPoints; the moments come from pcnerf::eval_gmoments_points.  No
+    gradient flows to the positions."""
+
+    @staticmethod
+    def forward(ctx, query_points, model, pts, table, z, noise, noise_std, eps, chunk, with_losses, divide, sub_num,
+                *params):
+        P = torch.ops.pcnerf
+        p = query_points(model, pts, z.shape[0], z.shape[1], chunk)
+        w, depth, fr, sl = P.composite(p, z, noise, noise_std, eps, table, 10, 11, 14, True)
+        if with_losses:
+            free, dl = P.child_losses(fr, sl, table, divide, sub_num)
+        else:
+            free = dl = torch.zeros((), dtype=torch.float32, device=z.device)
+        ctx.model, ctx.noise_std, ctx.eps = model, noise_std, eps
+        ctx.with_losses, ctx.sub = with_losses, (sub_num if divide else 0)
+        ctx.save_for_backward(pts, table, z, p, noise)
+        ctx.mark_non_differentiable(w)
+        return w, depth, free, dl
+
+    @staticmethod
+    def backward(ctx, g_w, g_depth, g_free, g_dl):
+        pts, table, z, p, noise = ctx.saved_tensors
+        if not ctx.with_losses:
+            g_free = g_dl = None
+        g_logit = _ops.composite_backward(p, z, noise, ctx.noise_std, ctx.eps, table if ctx.with_losses else None,
+                                          ctx.sub, g_depth, g_free, g_dl)
+        mom = torch.ops.pcnerf.eval_gmoments_points(pts, g_logit.view(-1))
+        return (None,) * 12 + _frozen_param_grads(ctx.model, mom)
+
+
 def check_frozen_eval(model, what: str) -> None:
     """The geometry gradient exists for the frozen eval network only: train-mode BatchNorm takes its statistics from
     the batch, which couples every sample's output to every other sample's position."""
@@ -176,7 +257,11 @@ def check_frozen_eval(model, what: str) -> None:
 class NofForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, *params):
-        p, ctx.fold = _ops.nof_forward_embedded(model, x, with_fold_state=True)
+        ctx.frozen = not model.training
+        if ctx.frozen:   # eval mode: the no-grad call itself (any eval path); nothing but x and p is kept
+            p, ctx.fold = _ops.nof_forward_embedded(model, x), None
+        else:
+            p, ctx.fold = _ops.nof_forward_embedded(model, x, with_fold_state=True)
         ctx.model = model
         ctx.save_for_backward(x, p)
         return p
@@ -184,7 +269,9 @@ class NofForward(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_p):
         x, p = ctx.saved_tensors
-        if ctx.fold is not None:
+        if ctx.frozen:
+            grads = _ops.nof_forward_eval_param_backward(ctx.model, x, p.reshape(-1), g_p.contiguous().reshape(-1))
+        elif ctx.fold is not None:
             grads = _ops.nof_forward_backward_fold(ctx.model, x, p.reshape(-1), g_p.contiguous().reshape(-1),
                                                    ctx.fold)
             ctx.fold = None
@@ -215,6 +302,13 @@ def needs_grad(model) -> bool:
 
 
 def check_trainable(model) -> None:
-    if not model.training:
-        raise NotImplementedError("gradients through the HIP NOF kernels are implemented for train-mode BatchNorm "
-                                  "(the reference trains with model.train()); call model.train() or use no_grad")
+    """Parameter gradients through the HIP NOF kernels exist in both BatchNorm modes, decided per module: train mode
+    (batch statistics: TrainPass / TrainPassPoints / NofForward's rematerialised backward) and eval mode (frozen
+    running statistics: FrozenPass / FrozenPassPoints / NofForward's eval branch).  What either needs is the uniform
+    affine BatchNorm1d configuration with running statistics the kernels implement."""
+    try:
+        _ops._bn_config(model)
+    except NotImplementedError as e:
+        mode = "train-mode" if model.training else "eval-mode (frozen BatchNorm)"
+        raise NotImplementedError(f"no {mode} parameter gradients through the HIP NOF kernels for this module: {e}; "
+                                  "use torch.no_grad()") from e

@@ -145,6 +145,17 @@ _SIGS = {
                                           c_int, c_int, vp, vp, vp, vp, vp, vp]),
     "pcnerf_nof_points_eval_backward": (c_int, [vp, i64, vp, vp, vp, vp]),
     "pcnerf_nof_query_eval_backward": (c_int, [vp, i64, c_int, vp, c_int, vp, vp, vp, vp]),
+    "pcnerf_nof_eval_pgrad_workspace_bytes": (c_size, [i64]),
+    "pcnerf_nof_eval_gmoments_rays": (c_int, [vp, i64, c_int, vp, c_int, vp, vp, c_size, vp, vp]),
+    "pcnerf_nof_eval_gmoments_points": (c_int, [vp, i64, vp, vp, c_size, vp, vp]),
+    "pcnerf_nof_eval_gmoments_embedded": (c_int, [vp, i64, vp, vp, vp, c_size, vp, vp]),
+    "pcnerf_nof_eval_param_grads": (c_int, [ctypes.POINTER(NofParams), c_float, vp, ctypes.POINTER(NofGrads), vp]),
+    "pcnerf_nof_query_eval_param_backward": (c_int, [vp, i64, c_int, vp, c_int, ctypes.POINTER(NofParams), c_float,
+                                                     vp, vp, c_size, ctypes.POINTER(NofGrads), vp]),
+    "pcnerf_nof_points_eval_param_backward": (c_int, [vp, i64, ctypes.POINTER(NofParams), c_float, vp, vp, c_size,
+                                                      ctypes.POINTER(NofGrads), vp]),
+    "pcnerf_nof_forward_eval_param_backward": (c_int, [vp, i64, ctypes.POINTER(NofParams), c_float, vp, vp, vp,
+                                                       c_size, ctypes.POINTER(NofGrads), vp]),
 }
 
 

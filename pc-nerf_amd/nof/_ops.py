@@ -1009,3 +1009,60 @@ def nof_forward_backward(model, x, p, g_p) -> list:
                                                 _f32(g_p).data_ptr(), ws.data_ptr(), ws.numel(), ctypes.byref(gs),
                                                 _stream(x)))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- frozen BatchNorm
+# Parameter gradients of the EVAL-mode network (include/pcnerf_hip.h, "eval-mode gradients to the parameters"): the
+# pass's moments m = sum_s g_s e_s, s0 = sum_s g_s, then one float64 pseudo-sample forward and backward.
+def _pgrad_workspace(device, total: int) -> torch.Tensor:
+    # a buffer of its own per call (float64: 8-byte aligned): the moments kernels of the two passes of one backward
+    # may be in flight together on different streams
+    nbytes = int(H.lib().pcnerf_nof_eval_pgrad_workspace_bytes(int(total)))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def eval_gmoments_rays(rays, z, g_logit) -> torch.Tensor:
+    """(64,) float64: sum_s g_s Embedding(o + d z_s) in [:63], sum_s g_s in [63] (pcnerf_nof_eval_gmoments_rays)."""
+    R, S = z.shape
+    mom = torch.zeros(64, dtype=torch.float64, device=z.device)
+    ws = _pgrad_workspace(z.device, R * S)
+    H.check(H.lib().pcnerf_nof_eval_gmoments_rays(rays.data_ptr(), R, rays.shape[1], z.data_ptr(), S,
+                                                  g_logit.data_ptr(), ws.data_ptr(), ws.numel() * 8, mom.data_ptr(),
+                                                  _stream(z)))
+    return mom
+
+
+def eval_gmoments_points(pts, g_logit) -> torch.Tensor:
+    """eval_gmoments_rays on explicit positions pts (N, 3), read verbatim (pcnerf_nof_eval_gmoments_points)."""
+    n = g_logit.numel()
+    mom = torch.zeros(64, dtype=torch.float64, device=pts.device)
+    ws = _pgrad_workspace(pts.device, n)
+    H.check(H.lib().pcnerf_nof_eval_gmoments_points(pts.data_ptr(), n, g_logit.data_ptr(), ws.data_ptr(),
+                                                    ws.numel() * 8, mom.data_ptr(), _stream(pts)))
+    return mom
+
+
+def eval_gmoments_embedded(emb, g_logit) -> torch.Tensor:
+    """eval_gmoments_rays on an embedded batch emb (N, 63) (pcnerf_nof_eval_gmoments_embedded, p = NULL)."""
+    n = emb.shape[0]
+    mom = torch.zeros(64, dtype=torch.float64, device=emb.device)
+    ws = _pgrad_workspace(emb.device, n)
+    H.check(H.lib().pcnerf_nof_eval_gmoments_embedded(emb.data_ptr(), n, None, g_logit.data_ptr(), ws.data_ptr(),
+                                                      ws.numel() * 8, mom.data_ptr(), _stream(emb)))
+    return mom
+
+
+def nof_forward_eval_param_backward(model, x, p, g_p) -> list:
+    """Parameter gradients (grad_params order) of NOF.forward(x) in eval mode given dL/dp
+    (pcnerf_nof_forward_eval_param_backward: both stages, dL/dlogit formed in the kernel)."""
+    L = H.lib()
+    x = _f32(x)
+    B = x.shape[0]
+    _, eps = _bn_config(model)
+    s, keep = _params(model)
+    gs, out = _grads_struct(model, x.device)
+    ws = _pgrad_workspace(x.device, B)
+    H.check(L.pcnerf_nof_forward_eval_param_backward(x.data_ptr(), B, ctypes.byref(s), eps, _f32(p).data_ptr(),
+                                                     _f32(g_p).data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                     ctypes.byref(gs), _stream(x)))
+    return out

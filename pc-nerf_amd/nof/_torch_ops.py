@@ -301,6 +301,94 @@ def _(rays, z, grad_logit, fold):
     return z.new_empty((z.shape[0], 6), dtype=torch.float32)
 
 
+# ----------------------------------------------------------------------------------------------- frozen BatchNorm
+# Parameter gradients of the eval-mode network: logit = a(theta) . e + c(theta), so the gradients of a pass are those of
+# one pseudo-sample with input m = sum_s g_s e_s and constants scaled by s0 = sum_s g_s (include/pcnerf_hip.h).  The
+# backward kernels of nof._autograd.FrozenPass / FrozenPassPoints; plain operators.
+def _gmoments_checked(op: str, *ts: Tensor) -> None:
+    _one_device(op, *ts)
+
+
+@torch.library.custom_op(f"{NS}::eval_gmoments_rays", mutates_args=())
+def eval_gmoments_rays(rays: Tensor, z: Tensor, grad_logit: Tensor) -> Tensor:
+    """(64,) float64: [:63] = sum_s g_s Embedding(o + d z_s), [63] = sum_s g_s over the pass (autograd of
+    render.py:44-51 to the eval network's parameters, first stage): rays (R, >=6), z (R, S), grad_logit (R, S)."""
+    op = "eval_gmoments_rays"
+    _need(op, "z", z, (None, ("min", 1)))
+    _need(op, "rays", rays, (z.shape[0], ("min", 6)))
+    _need(op, "grad_logit", grad_logit, tuple(z.shape))
+    _gmoments_checked(op, rays, z, grad_logit)
+    return _ops.eval_gmoments_rays(rays, z, grad_logit)
+
+
+@eval_gmoments_rays.register_fake
+def _(rays, z, grad_logit):
+    return z.new_empty((64,), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{NS}::eval_gmoments_points", mutates_args=())
+def eval_gmoments_points(pts: Tensor, grad_logit: Tensor) -> Tensor:
+    """eval_gmoments_rays on explicit positions, read verbatim: pts (N, 3) or (R, S, 3), grad_logit (N,) or (R, S)."""
+    op = "eval_gmoments_points"
+    H.require_device(pts)
+    if pts.dim() not in (2, 3) or pts.shape[-1] != 3:
+        raise RuntimeError(f"pcnerf::{op}: pts has shape {tuple(pts.shape)}, expected (N, 3) or (R, S, 3)")
+    _need(op, "pts", pts, tuple(pts.shape))
+    _need(op, "grad_logit", grad_logit, tuple(pts.shape[:-1]))
+    _gmoments_checked(op, pts, grad_logit)
+    return _ops.eval_gmoments_points(pts, grad_logit)
+
+
+@eval_gmoments_points.register_fake
+def _(pts, grad_logit):
+    return pts.new_empty((64,), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{NS}::eval_gmoments_embedded", mutates_args=())
+def eval_gmoments_embedded(emb: Tensor, grad_logit: Tensor) -> Tensor:
+    """eval_gmoments_rays on an embedded batch (models.py:103-123's input): emb (N, 63), grad_logit (N,)."""
+    op = "eval_gmoments_embedded"
+    _need(op, "emb", emb, (None, 63))
+    _need(op, "grad_logit", grad_logit, (emb.shape[0],))
+    _gmoments_checked(op, emb, grad_logit)
+    return _ops.eval_gmoments_embedded(emb, grad_logit)
+
+
+@eval_gmoments_embedded.register_fake
+def _(emb, grad_logit):
+    return emb.new_empty((64,), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{NS}::eval_param_grads", mutates_args=())
+def eval_param_grads(params: list[Tensor], mom: Tensor, eps: float) -> list[Tensor]:
+    """The 34 parameter gradients (nof._ops.grad_params order: lin_w[8], lin_b[8], bn_w[8], bn_b[8], out_w, out_b) of
+    the eval network's pseudo-sample with moments ``mom`` (pcnerf::eval_gmoments_*), float64 algebra rounded to
+    float32 once (pcnerf_nof_eval_param_grads).  params: the 50 tensors in pcnerf::pack_eval's order; the running
+    statistics are read, never written."""
+    op = "eval_param_grads"
+    s = _params_struct(op, params)
+    _need(op, "mom", mom, (64,), torch.float64)
+    _one_device(op, params[0], mom)
+    import ctypes
+    shapes = _param_shapes()
+    # an operator's outputs own their memory (no views of one buffer): 34 zeroed tensors the kernel adds into
+    out = [torch.zeros(shp, dtype=torch.float32, device=mom.device) for shp in shapes[:32] + shapes[48:]]
+    g = H.NofGrads()
+    for i in range(8):
+        g.lin_w[i], g.lin_b[i] = out[i].data_ptr(), out[8 + i].data_ptr()
+        g.bn_w[i], g.bn_b[i] = out[16 + i].data_ptr(), out[24 + i].data_ptr()
+    g.out_w, g.out_b = out[32].data_ptr(), out[33].data_ptr()
+    H.check(H.lib().pcnerf_nof_eval_param_grads(ctypes.byref(s), float(eps), mom.data_ptr(), ctypes.byref(g),
+                                                H.stream_of(mom)))
+    return out
+
+
+@eval_param_grads.register_fake
+def _(params, mom, eps):
+    shapes = _param_shapes()
+    return [mom.new_empty(s, dtype=torch.float32) for s in shapes[:32] + shapes[48:]]
+
+
 # ----------------------------------------------------------------------------------------------- compositing
 @torch.library.custom_op(f"{NS}::composite", mutates_args=())
 def composite(p: Tensor, z: Tensor, noise: Optional[Tensor], noise_std: float, eps: float, rays: Optional[Tensor],
@@ -428,4 +516,5 @@ def op_names() -> list:
     """The registered operator names (tests)."""
     return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "query_points_eval", "composite",
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
-            "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval"]
+            "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval", "eval_gmoments_rays",
+            "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads"]

@@ -84,6 +84,9 @@ def build_parser() -> argparse.ArgumentParser:
     a('--frame_sparsity', type=int, default=20, help="train-frame rule of ipb2dmapping.py:632-640 (percent)")
     a('--max_steps', type=int, default=0, help="stop after this many training steps (0: run every epoch)")
     a('--log_path', type=str, default=None, help="JSON-lines log of every step / validation")
+    a('--freeze_bn', default=False, action="store_true",
+      help="train with frozen BatchNorm: the training steps run both networks in eval mode (running statistics "
+           "used and left unchanged, every weight trains)")
     return p
 
 

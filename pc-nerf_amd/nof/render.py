@@ -20,7 +20,11 @@ Differences from the reference, all deliberate:
   * gradients: ``render_rays_train`` is differentiable (train-mode networks): with autograd enabled and
     parameters requiring grad, each pass runs as ``nof._autograd.TrainPass`` whose backward is the HIP
     compositing backward + the NOF backward (chunks recomputed), so ``loss.backward()`` of train_kitti.py:155
-    fills ``.grad`` of both networks.  ``render_rays_val`` and ``inference_val`` are differentiable with respect
+    fills ``.grad`` of both networks.  An EVAL-mode module whose parameters require grad trains with frozen
+    BatchNorm (running statistics used and left untouched), decided per module: its pass of ``render_rays_train`` /
+    ``inference_train`` runs as ``nof._autograd.FrozenPass`` / ``FrozenPassPoints`` -- the eval query of the
+    no-grad call (same output bits), then compositing backward + pcnerf::eval_gmoments_* +
+    pcnerf::eval_param_grads.  ``render_rays_val`` and ``inference_val`` are differentiable with respect
     to their GEOMETRY on frozen eval-mode networks: when ``rays`` / ``samples_xy`` requires grad, each pass runs as
     ``nof._autograd.EvalPass`` / ``EvalPassPoints``, whose backward is the HIP compositing backward + the eval
     network's position gradient (pcnerf_nof_query_eval_backward / pcnerf_nof_points_eval_backward), so
@@ -221,15 +225,21 @@ def inference_train(model: NOF, embedding_xy: Embedding, samples_xy: torch.Tenso
                     *, rng=None):
     """render.py:38-163 -> (child_free_loss, child_depth_loss, depth_final (R,), weights_origin (R, S)).  The losses
     are CPU ``torch.tensor(0.0)`` when use_child_nerf_loss != 1 and have shape (1,) in the divide branch.
-    Differentiable under autograd with a train-mode module (the conditions of render_rays_train); no gradient flows
-    to samples_xy.  ``near_far_point``, ``ray_class`` and ``isval`` are accepted and unused."""
+    Differentiable under autograd with respect to the module's parameters, in train mode (batch statistics) or in
+    eval mode (frozen BatchNorm, nof._autograd.FrozenPassPoints), as render_rays_train; no gradient flows to
+    samples_xy.  ``near_far_point``, ``ray_class`` and ``isval`` are accepted and unused."""
     pts, z = _check_points_inputs(model, embedding_xy, samples_xy, z_vals, near_far_child, differentiable=True)
     R, S = z.shape
     with_losses = use_child_nerf_loss == 1
     divide = use_child_nerf_divide == 1
     table = _child_table(rays, near_far_child, range_readings, R, divide) if with_losses else None
     noise = _noise(rng, "noise", z, noise_std)
-    if _autograd.needs_grad(model):
+    if _autograd.needs_grad(model) and not model.training:   # frozen BatchNorm
+        w, depth, free, dl = _autograd.FrozenPassPoints.apply(_query_points, model, pts, table, z, noise,
+                                                              float(noise_std), float(epsilon), int(chunk),
+                                                              with_losses, divide, int(sub_nerf_test_num),
+                                                              *_ops.grad_params(model))
+    elif _autograd.needs_grad(model):
         sub = int(sub_nerf_test_num) if divide else 0
         w, depth, free, dl = _autograd.TrainPassPoints.apply(model, pts, table, z, noise, float(noise_std),
                                                              float(epsilon), int(chunk), with_losses, sub,
@@ -285,13 +295,22 @@ def render_rays_train(model: NOF, model_fine: NOF, embedding_xy: Embedding, rays
                       isval=False, issegmentated=0, childnerf_ratio=0.5, use_child_nerf_divide=0,
                       use_child_nerf_loss=0, *, rng=None):
     """render.py:416-482 -> {'child_free_loss_fine', 'child_depth_loss_fine', 'depth_fine', 'child_free_loss',
-    'child_depth_loss', 'depth'}."""
+    'child_depth_loss', 'depth'}.  Under autograd each network takes the route of its own mode: train mode the
+    rematerialised backward, eval mode the frozen-BatchNorm backward (coarse in train and fine in eval mode in one
+    call is legal); no gradient goes to the rays."""
     rays = _check_inputs(model, model_fine, embedding_xy, rays, 15, differentiable=True)
     R = rays.shape[0]
     z = _coarse(rays, N_samples, issegmentated, childnerf_ratio, perturb, rng)
     with_losses = use_child_nerf_loss == 1
 
     def one_pass(m, z, noise_key):
+        if _autograd.needs_grad(m) and not m.training:   # frozen BatchNorm: decided per module
+            w, depth, free, dl = _autograd.FrozenPass.apply(
+                _query, m, rays, z, _noise(rng, noise_key, z, noise_std), float(noise_std), EPSILON, int(chunk),
+                with_losses, use_child_nerf_divide == 1, int(sub_nerf_test_num), *_ops.grad_params(m))
+            if not with_losses:
+                free, dl = torch.tensor(0.0), torch.tensor(0.0)
+            return w, depth, free, dl
         if _autograd.needs_grad(m):
             noise = _noise(rng, noise_key, z, noise_std)
             sub = int(sub_nerf_test_num) if use_child_nerf_divide == 1 else 0

@@ -211,13 +211,15 @@ def validate(system, fh=None, epoch=-1):
     return out
 
 
-def fit(system, max_steps=0, log_path=None, ckpt_dir=None):
-    """Trainer.fit (train_kitti.py:286-299) for one process, or one rank of a data-parallel job."""
+def fit(system, max_steps=0, log_path=None, ckpt_dir=None, *, freeze_bn=False):
+    """Trainer.fit (train_kitti.py:286-299) for one process, or one rank of a data-parallel job.  ``freeze_bn``: the
+    training steps run both networks in eval mode -- BatchNorm normalises with its running statistics, which stay as
+    they are, and every weight trains (fine-tuning a trained block; nof._autograd.FrozenPass)."""
     import torch.distributed as dist
     h = system.hparams
     ddp = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if ddp else (0, 1)
-    bns = BnSync() if ddp else None
+    bns = BnSync() if (ddp and not freeze_bn) else None   # frozen statistics: nothing to synchronise
     system.prepare_data()
     opt, sched = system.configure_optimizers()
     params = system.parameters()
@@ -229,8 +231,8 @@ def fit(system, max_steps=0, log_path=None, ckpt_dir=None):
     step = 0
     t0 = time.perf_counter()
     for epoch in range(h.num_epochs):
-        system.nof_coarse.train()
-        system.nof_fine.train()
+        system.nof_coarse.train(not freeze_bn)
+        system.nof_fine.train(not freeze_bn)
         perm = torch.randperm(n, device=system.device, generator=gen)   # same order on every rank (same seed)
         gb = h.batch_size * world
         ep_loss = []
@@ -240,7 +242,7 @@ def fit(system, max_steps=0, log_path=None, ckpt_dir=None):
                 continue
             idx = shard_batch(glob, rank, world)
             opt.zero_grad(set_to_none=True)
-            if ddp:
+            if bns is not None:
                 with bns.record():
                     loss, logs = system.training_step(system.train_dataset[idx], b)
             else:
@@ -248,7 +250,8 @@ def fit(system, max_steps=0, log_path=None, ckpt_dir=None):
             loss.sum().backward()
             if ddp:
                 allreduce_grads(params)
-                bns.sync()
+                if bns is not None:
+                    bns.sync()
             opt.step()
             step += 1
             ep_loss.append(loss.detach())
@@ -290,7 +293,7 @@ def main(argv=None):
     system = NOFSystem(h)
     out_dir = os.path.join("logs", h.exp_name) if not h.result_path else h.result_path
     res = fit(system, max_steps=h.max_steps, log_path=h.log_path,
-              ckpt_dir=os.path.join(out_dir, "checkpoints"))
+              ckpt_dir=os.path.join(out_dir, "checkpoints"), freeze_bn=bool(h.freeze_bn))
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res))
     if world > 1:
