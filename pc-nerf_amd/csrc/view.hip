@@ -252,7 +252,17 @@ __global__ void k_walk_finish(const int64_t* __restrict__ other, int64_t n, cons
       flag[i] = 1;
       i += 1;
     } else if (o > 0) {
-      if (i + o >= n) break;  // the reference would raise IndexError here
+      if (i + o >= n) {
+        // the last group runs past the end.  The reference raises IndexError only where it READS a row that is
+        // not there: with the peak on the head, or on an inner row it reaches before the end, it flags that row
+        // and the walk is over (i + o + 1 > n); otherwise nothing of this group is flagged
+        int64_t pick = -1;
+        if (at_peak[i]) pick = i;
+        for (int64_t j = i + 1; pick < 0 && j < n; ++j)
+          if (at_peak[j]) pick = j;
+        if (pick >= 0) flag[pick] = 1;
+        break;
+      }
       pick_group(at_peak, wsum, flag, i, o);
       i += o + 1;
     } else {

@@ -11,6 +11,7 @@ import torch
 
 from conftest import golden
 from gradcheck import _report
+from parity_helpers import knife_edge
 from nof import synthetic as syn
 from nof.networks import Embedding, NOF_coarse, NOF_fine
 from nof import render as R
@@ -121,20 +122,6 @@ def test_layered_split_range_guard():
             close(p.reshape(-1), ref, 1e-4, 1e-6, f"p beyond fp16 range ({m})")
     finally:
         ops.set_train_math(prev)
-
-
-def knife_edge(bins, weights, u):
-    """Samples whose bin has cdf_hi - cdf_lo within 4 ulp of the reference's 1e-5 threshold (render.py:408): there
-    the branch depends on the last bit of the normaliser sum, whose order torch CPU fixes per ISA."""
-    w = weights + 1e-5
-    cdf = torch.cat([torch.zeros_like(w[:, :1]), torch.cumsum(w / w.sum(-1, keepdim=True), -1)], -1)
-    inds = torch.searchsorted(cdf, u, right=True)
-    lo = torch.gather(cdf, 1, torch.clamp(inds - 1, min=0))
-    hi = torch.gather(cdf, 1, torch.clamp(inds, max=cdf.shape[-1] - 1))
-    ulp = torch.finfo(torch.float32).eps * torch.maximum(hi.abs(), torch.tensor(1e-30))
-    near = ((hi - lo) - 1e-5).abs() <= 4 * ulp
-    # a neighbouring cdf entry within an ulp of u can also move the bin
-    return near | ((u - lo).abs() <= 2 * ulp) | ((hi - u).abs() <= 2 * ulp)
 
 
 def test_sample_pdf():

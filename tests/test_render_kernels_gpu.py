@@ -14,38 +14,15 @@ import numpy as np
 import pytest
 import torch
 
-from gradcheck import _report
 from nof import _hip as H
 from nof import _ops
 
 import render_f64 as F
 import render_inputs as I
+from parity_helpers import FLOOR, Tally
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-FLOOR = 2.4e-7
-
-
-class Tally:
-    """Collects every quantity's e_hip / e32 of one test, reports them, and fails once at the end with all misses."""
-
-    def __init__(self, test):
-        self.test, self.bad, self.worst = test, [], 0.0
-
-    def check(self, case, name, x_hip, q32, q64, cap=I.E32_CAP):
-        e_hip, e32 = F.err(x_hip, q64), F.err(q32, q64)
-        tol = max(4 * e32, FLOOR)
-        self.worst = max(self.worst, e_hip / tol)
-        _report({"test": self.test, "case": case, "quantity": name, "e_hip": e_hip, "e32": e32, "tol": tol})
-        if e32 > cap:
-            self.bad.append(f"{case} {name}: float32 reference off by {e32:.3g} > {cap:.3g} (inputs too hard)")
-        if not e_hip <= tol:
-            self.bad.append(f"{case} {name}: e_hip {e_hip:.3g} > max(4 x e32 {e32:.3g}, {FLOOR})")
-
-    def done(self):
-        _report({"test": self.test, "worst_e_hip_over_tol": self.worst, "failed": len(self.bad)})
-        assert not self.bad, "\n".join(self.bad)
-
 
 @pytest.fixture
 def group(request):
