@@ -67,8 +67,10 @@ int pcnerf_set_query_geometry(int geometry);
 
 /* Form of the store-less train-mode query where it runs as the 8-wave workgroup with the 2-slot ring (query geometry
  * -1 or 1), process-wide; returns the previous setting, or -2 for an invalid one.  -1 (default): the measured
- * default (form 2).  0: 6 sample blocks, 96 samples per pass over the weight image.  2: 7 sample blocks, 112 samples
- * per pass.  (1 was a half-skewed schedule of form 0; it measured slower and is not built: refused.)  Every form
+ * default (form 4; form 2 on a device that cannot give a workgroup 163,840 B of LDS, with a message in
+ * pcnerf_last_error).  0: 6 sample blocks, 96 samples per pass over the weight image.  2: 7 sample blocks, 112 samples
+ * per pass.  4: 8 sample blocks, 128 samples per pass, the activations and encoding operands as the CU's whole LDS.
+ * (1 was a half-skewed schedule of form 0; it measured slower and is not built: refused, as are 3 and 5.)  Every form
  * computes the same bits; for A/B timing and the bit-identity tests. */
 int pcnerf_set_train_query_form(int form);
 

@@ -257,8 +257,8 @@ __device__ __forceinline__ void eh_split8(const float (&v)[8], eh_f16x8& hi, eh_
 // each wave streams only its own neurons' weights from L2 (an R3-slot register ring, R3 - 1 k-steps of prefetch, no
 // barrier) and each A operand feeds SB sample blocks.  Two geometries, two waves per SIMD on a CU either way:
 // <NW 4, SB 3> (two workgroups of 48 samples per CU, each streaming the whole image: the eval query and the
-// store-writing train query) and <NW 8, SB 6 or 7> (one workgroup of 96 or 112 samples, one pass over the image: the
-// store-less train query, 7 blocks by default -- EH3_TRAIN_FORM below);
+// store-writing train query) and <NW 8, SB 6, 7 or 8> (one workgroup of 96, 112 or 128 samples, one pass over the image:
+// the store-less train query, 8 blocks by default -- EH3_TRAIN_FORM below);
 // every accumulator sees the same products in the same order in all of them (the formulas below are for NW = 4: J = 4);
 // the layer outputs go through LDS as the next layer's split B operands ([k-step][sample block][part][lane],
 // 16 KiB per sample block), two barriers per layer.  The encoding lives in LDS as layer 0's split B operands; layer 4 re-splits it
@@ -325,7 +325,7 @@ static_assert(96 % (16 * EH3_SB) == 0, "store_layer_bytes (pcnerf_internal.h) pa
 // The wide geometry <NW = 8, SB = 6>: the same 96 samples per CU as ONE workgroup of 8 waves, wave w owning neuron
 // blocks 2w, 2w + 1 (J = 2), so a CU streams the weight image once per 96 samples instead of twice; still two waves
 // per SIMD, but the two halves no longer run independent phases.  ~140 KiB of LDS, __launch_bounds__(512, 1).
-// (The store-less train query runs it with 7 blocks, 112 samples, by default: EH3_SB_WIDE7 below.)
+// (The store-less train query runs it with 8 blocks, 128 samples, by default: EH3_SB_WIDE8 below.)
 constexpr int EH3_SB_WIDE = 6;
 static_assert(96 % (16 * EH3_SB_WIDE) == 0, "store_layer_bytes pads a chunk to whole 96-sample blocks");
 // k_nof_eval_h3: weight-ring slots (prefetch distance R3 - 1 k-steps of 32).  The ring index is pos % R3 with pos a
@@ -370,9 +370,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   // J neuron blocks per wave, JP output k-steps per wave, WPG waves per 64-neuron group of occ_out's sum
   constexpr int NT = 64 * NW, J = 16 / NW, JP = J / 2, WPG = NW / 4, NS = 16 * SB, D3 = R3 - 1;
   constexpr bool ORD = TR;
+  // DIET (the 8-block form of the 8-wave store-less train query, pcnerf_set_train_query_form 4): act + eb alone are
+  // the CU's 163,840 B of LDS, so nothing else lives there -- the BatchNorm coefficients come straight from `coef`
+  // (L2) into registers one k-step before each layer end, spos / sx0s sit in act behind the encoding staging area
+  // (act is not written before the barrier after layer 0's MFMAs; sx0 is copied to registers before that), pdot in
+  // eb behind the occ_out hand-over.  Same operands into the same fmas: same bits.
+  constexpr bool DIET = TR && !ST && NW == 8 && SB == 8;
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
   __shared__ eh_f16x8 act[8][SB][2][64];
   __shared__ eh_f16x8 eb[2][SB][2][64];   // the encoding's B operands at the layer-0 scale (sx0)
+  static_assert(!DIET || sizeof(act) + sizeof(eb) == 163840, "the 8-block form: act + eb are the CU's LDS");
   __shared__ int sx0s[NS];
   __shared__ __attribute__((aligned(16))) float sbias[(TR ? 16 : 8) * 256];
   __shared__ float emax[NS];
@@ -381,6 +388,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   __shared__ float spos[NS][3];
   // TR with the store: the raw biases of two consecutive layers (slot L & 1), each loaded one layer ahead
   __shared__ __attribute__((aligned(16))) float sbraw[TR ? 2 : 1][TR ? 256 : 4];
+  // DIET: [sample][65] encoding staging | spos | sx0s in act, hand | pdot in eb; sbias is not referenced
+  float* const actf = reinterpret_cast<float*>(&act[0][0][0][0]);
+  float* const ebf = reinterpret_cast<float*>(&eb[0][0][0][0]);
+  float (*const sposv)[3] = DIET ? reinterpret_cast<float (*)[3]>(actf + NS * 65) : spos;
+  int* const sx0v = DIET ? reinterpret_cast<int*>(actf + NS * 68) : sx0s;
+  float (*const pdotv)[NS] = DIET ? reinterpret_cast<float (*)[NS]>(ebf + 4 * SB * 64) : pdot;
   const int t = threadIdx.x, w = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, g = lane >> 4, li = lane & 15;
   const int cy = (int)blockIdx.y + cy0;   // the BatchNorm chunk
   const int64_t cb = TR ? (int64_t)cy * chunk : 0;
@@ -433,7 +446,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
     sbraw[0][t] = W[OFF_BIAS + t];
     sbraw[TR ? 1 : 0][t] = W[OFF_BIAS + 256 + t];
   }
-  if (TR) {
+  if (DIET) {
+    // (no coefficient image in LDS: coef_load / epi_tr below)
+  } else if (TR) {
     const f32x4_* cf = reinterpret_cast<const f32x4_*>(coef + cy * (size_t)TQ_COEF_FLOATS);
     constexpr int CM = 16 * 256 / 4 / NT;
     f32x4_ cv[CM];
@@ -452,7 +467,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
       reinterpret_cast<f32x4_*>(sbias)[i] = reinterpret_cast<const f32x4_*>(W + OFF_BIAS)[i];
   }
   float* const encf = reinterpret_cast<float*>(&act[0][0][0][0]);   // [sample][65]
-  static_assert(sizeof(act) >= NS * 65 * sizeof(float), "encoding staging area");
+  static_assert(sizeof(act) >= NS * (65 + (DIET ? 4 : 0)) * sizeof(float), "encoding staging area (DIET: + spos, sx0s)");
   if (PT || !ein) {
     if (t < NS) {
       float p[3];
@@ -460,7 +475,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
       else sample_point(rr, rz, p);
 #pragma unroll
       for (int m = 0; m < 3; ++m) {
-        spos[t][m] = p[m];
+        sposv[t][m] = p[m];
         encf[t * 65 + m] = p[m];
       }
       encf[t * 65 + 63] = 0.0f;
@@ -469,7 +484,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
     for (int i = t; i < NS * 30; i += NT) {
       const int sm = i / 30, r = i - 30 * sm, k = r / 3, m = r - 3 * k;
       float sv, cv;
-      sincosf((float)(1 << k) * spos[sm][m], &sv, &cv);
+      sincosf((float)(1 << k) * sposv[sm][m], &sv, &cv);
       encf[sm * 65 + 3 + 6 * k + m] = sv;
       encf[sm * 65 + 6 + 6 * k + m] = cv;
     }
@@ -506,12 +521,30 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
         eb[s][t >> 4][1][(t & 15) + 16 * gg] = mid;
       }
     if (!TR) emax[t] = m;
-    sx0s[t] = sx0;
+    sx0v[t] = sx0;
   }
   __syncthreads();
   int sxl[SB];   // the per-sample scale of the current layer's B operands (this lane's sample of each block)
 #pragma unroll
-  for (int sb = 0; sb < SB; ++sb) sxl[sb] = sx0s[16 * sb + li];
+  for (int sb = 0; sb < SB; ++sb) sxl[sb] = sx0v[16 * sb + li];
+  int sx0l[DIET ? SB : 1];   // DIET: sx0s leaves LDS with act's first write, so every lane keeps its own
+  if (DIET) {
+#pragma unroll
+    for (int sb = 0; sb < SB; ++sb) sx0l[sb] = sxl[sb];
+  }
+  // DIET: this lane's BatchNorm coefficients of the layer that ends next (alpha, beta'' of its J x 4 neurons, raw),
+  // loaded from coef one k-step before the layer end; epi_tr scales them as the other forms' prologue does
+  f32x4_ cfa[J], cfb[J];
+  auto coef_load = [&](int L) __attribute__((always_inline)) {
+    if constexpr (DIET) {
+      const float* c = coef + cy * (size_t)TQ_COEF_FLOATS + 512 * L + 16 * J * w + 4 * g;
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        cfa[j] = *reinterpret_cast<const f32x4_*>(c + 16 * j);
+        cfb[j] = *reinterpret_cast<const f32x4_*>(c + 256 + 16 * j);
+      }
+    }
+  };
   f32x4_ acc[J][SB];
   int gk = 0;
   // one encoding k-step (layers 0 and 4)
@@ -558,7 +591,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   // the 8 hidden k-steps of a layer, software-pipelined: per k-step the products run in the order Wh.xm, Wh.xh,
   // Wm.xh, and k-step s + 1's xm is read from LDS once Wh.xm of s is issued, its xh once Wm.xh of s is -- every LDS
   // read has at least 24 MFMAs in flight to cover it
-  auto hidden_ksteps = [&](int pos0, bool first) __attribute__((always_inline)) {
+  auto hidden_ksteps = [&](int pos0, bool first, int L) __attribute__((always_inline)) {
     eh_f16x8 bh[SB], bm[SB];
 #pragma unroll
     for (int sb = 0; sb < SB; ++sb) {
@@ -568,6 +601,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int pos = pos0 + s;
+      if (s == 7) coef_load(L);
       load_w(wr[(pos + D3) % R3], gk + D3);
       const eh_f16x8 (&wc)[J][2] = wr[pos % R3];
 #pragma unroll
@@ -678,6 +712,32 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
   };
   auto epi_tr = [&](int L, auto PS) __attribute__((always_inline)) {
     constexpr bool ps = decltype(PS)::value;
+    if constexpr (DIET) {
+      // the coefficients at the scales the other forms' prologue gives them (uniform exponents, ldexpf exact), once
+      // per layer: they depend on j only
+      const int ea = sxB[L] - sw[L] - ((L == 0 || L == 4) ? 0 : sxB[L > 0 ? L - 1 : 0]), ebt = sxB[L];
+      f32x4_ a[J], b[J];
+#pragma unroll
+      for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          a[j][q] = ldexpf(cfa[j][q], ea);
+          b[j][q] = ldexpf(cfb[j][q], ebt);
+        }
+#pragma unroll
+      for (int sb = 0; sb < SB; ++sb) {
+        const float us = ps ? ldexpf(1.0f, -sxl[sb]) : 1.0f;
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float v = acc[j][sb][q];
+            if (ps) v *= us;
+            acc[j][sb][q] = __builtin_fmaf(v, a[j][q], b[j][q]);
+          }
+      }
+      return;
+    }
 #pragma unroll
     for (int sb = 0; sb < SB; ++sb) {
       const float us = ps ? ldexpf(1.0f, -sxl[sb]) : 1.0f;
@@ -701,7 +761,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
     }
   };
 #pragma unroll
-  for (int s = 0; s < 2; ++s) kstep_enc(s, s, s == 0);
+  for (int s = 0; s < 2; ++s) {
+    if (s == 1) coef_load(0);
+    kstep_enc(s, s, s == 0);
+  }
   if (TR) {
     epi_tr(0, std::true_type{});
     float xs[SB];
@@ -733,7 +796,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
         float xs[SB];
 #pragma unroll
         for (int sb = 0; sb < SB; ++sb) {
-          const int sx0 = sx0s[16 * sb + li];
+          const int sx0 = DIET ? sx0l[sb] : sx0s[16 * sb + li];
           sxl[sb] = L == 3 ? sx0 : sxB[L];
           xs[sb] = ldexpf(1.0f, sx0 - sxB[3]);
         }
@@ -759,18 +822,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
 #pragma unroll 1
   for (int L = 1; L <= 3; ++L) {
     if (TR) bias_load(L);
-    hidden_ksteps(eh3_start(1) % R3, true);
+    hidden_ksteps(eh3_start(1) % R3, true, L);
     layer_end(L);
   }
   if (TR) bias_load(4);
 #pragma unroll
   for (int s = 0; s < 2; ++s) kstep_enc(s, eh3_start(4) % R3 + s, s == 0);
-  hidden_ksteps((eh3_start(4) + 2) % R3, false);
+  hidden_ksteps((eh3_start(4) + 2) % R3, false, 4);
   layer_end(4);
 #pragma unroll 1
   for (int L = 5; L <= 7; ++L) {
     if (TR) bias_load(L);
-    hidden_ksteps(eh3_start(5) % R3, true);
+    hidden_ksteps(eh3_start(5) % R3, true, L);
     layer_end(L);
   }
   // occ_out: each 64-neuron group's fma chain per lane and sample block (j, q ascending), the two cross-lane adds,
@@ -788,7 +851,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
     return part;
   };
   float (*const hand)[SB][64] = reinterpret_cast<float (*)[SB][64]>(&eb[0][0][0][0]);
-  static_assert(sizeof(eb) >= 4 * SB * 64 * sizeof(float), "occ_out handover area");
+  static_assert(sizeof(eb) >= (4 * SB * 64 + (DIET ? 4 * NS : 0)) * sizeof(float), "occ_out handover area (DIET: + pdot)");
   if (WPG == 2) {
     if (!(w & 1)) {
 #pragma unroll
@@ -802,12 +865,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? EH3_WG_PER_CU : 1) void k_nof_ev
       float part = occ_chain(sb, WPG == 1 ? 0.0f : hand[w >> 1][sb][lane]);
       part += __shfl_xor(part, 16, 64);
       part += __shfl_xor(part, 32, 64);
-      if (g == 0) pdot[w / WPG][16 * sb + li] = part;
+      if (g == 0) pdotv[w / WPG][16 * sb + li] = part;
     }
   }
   __syncthreads();
   if (t < NS && s0 + t < send) {
-    const float logit = ((pdot[0][t] + pdot[1][t]) + (pdot[2][t] + pdot[3][t])) + W[OFF_BOUT];
+    const float logit = ((pdotv[0][t] + pdotv[1][t]) + (pdotv[2][t] + pdotv[3][t])) + W[OFF_BOUT];
     p_out[s0 + t] = sigmoid_ref(logit);
   }
 }
@@ -826,20 +889,59 @@ constexpr int EH3_GEOM_EVAL = 0, EH3_GEOM_TRAIN = 1;
 // Form of the store-less train query where it runs in the 8-wave geometry with the 2-slot ring (geometry -1 or 1;
 // pcnerf_set_train_query_form): 0 = 6 sample blocks (96 samples per pass over the weight image), 2 = 7 sample blocks
 // (112 samples per pass: 6/7 of the L2 weight stream per sample; 163,328 B of LDS -- the train form without the store
-// allocates no smax / emax / sbraw, so it just fits the CU's 160 KiB; 213 VGPRs); -1 = the measured default, form 2
-// (config 2 forward 77.63 -> 76.21 ms, profiles/TRAIN_QUERY_FORM.md).  1 was the half-skewed form: measured slower,
-// not built (HISTORY.md).  Same bits in every form (tests/test_train_query_form_gpu.py).
+// allocates no smax / emax / sbraw, so it just fits the CU's 160 KiB; 213 VGPRs; config 2 forward 77.63 -> 76.21 ms),
+// 4 = 8 sample blocks (128 samples per pass: 7/8 of form 2's stream; act + eb are the CU's whole 163,840 B of LDS, the
+// small arrays and the coefficient image live elsewhere -- DIET in the kernel; 250 VGPRs, no spills); -1 = the
+// measured default, form 4 (config 2 forward 76.84 -> 75.00 ms, profiles/TRAIN_QUERY_FORM.md).  No 9th block fits:
+// the weight-stream lever ends here in this decomposition.  1 was the half-skewed form: measured slower, not built
+// (HISTORY.md); 3 was never built.  Same bits in every form (tests/test_train_query_form_gpu.py,
+// tests/test_train_query_form8_gpu.py).
 static int g_train_query_form = -1;
-constexpr int EH3_TRAIN_FORM = 2;
+constexpr int EH3_TRAIN_FORM = 4;
 constexpr int EH3_SB_WIDE7 = 7;
+constexpr int EH3_SB_WIDE8 = 8;
+
+// Form 4's 160 KiB of static LDS against the device's limit, asked once per process and point source: where it cannot
+// be launched the default falls back to form 2 (a message in pcnerf_last_error), and selecting 4 is an error.
+template <bool PT>
+static bool form8_launchable() {
+  static const bool ok = [] {
+    hipFuncAttributes fa;
+    int dev = 0, lim = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+        hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(
+                                      &k_nof_eval_h3<true, false, 8, EH3_SB_WIDE8, EH3_RING, PT>)) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    return fa.sharedSizeBytes <= (size_t)lim;
+  }();
+  return ok;
+}
 
 // launches k_nof_eval_h3<TR, false> in geometry geom: `rows` grid rows (BatchNorm chunks) of `span` samples each
 // (PT: the point source, the positions in the kernel's `rays` argument)
 template <bool TR, bool PT, typename... Args>
 static void launch_h3(int geom, int64_t span, unsigned rows, hipStream_t s, Args... args) {
   const bool wide = geom & 1, deep = geom & 2;
-  if constexpr (TR) {   // the 7-block form of the 8-wave train query (pcnerf_set_train_query_form)
-    if (wide && !deep && (g_train_query_form < 0 ? EH3_TRAIN_FORM : g_train_query_form) == 2) {
+  if constexpr (TR) {   // the 7- and 8-block forms of the 8-wave train query (pcnerf_set_train_query_form)
+    int form = g_train_query_form < 0 ? EH3_TRAIN_FORM : g_train_query_form;
+    if (wide && !deep && form == 4 && !form8_launchable<PT>()) {
+      if (g_train_query_form == 4)
+        throw std::runtime_error("train query: form 4 needs 163,840 B of LDS per workgroup, more than this device "
+                                 "gives");
+      set_error("train query: form 4 (163,840 B of LDS per workgroup) cannot be launched on this device; the "
+                "default falls back to form 2");
+      form = 2;
+    }
+    if (wide && !deep && form == 4) {
+      const int64_t ns8 = 16 * EH3_SB_WIDE8;
+      hipLaunchKernelGGL((k_nof_eval_h3<true, false, 8, EH3_SB_WIDE8, EH3_RING, PT>),
+                         dim3((unsigned)((span + ns8 - 1) / ns8), rows), dim3(512), 0, s, args...);
+      return;
+    }
+    if (wide && !deep && form == 2) {
       const int64_t ns7 = 16 * EH3_SB_WIDE7;
       hipLaunchKernelGGL((k_nof_eval_h3<true, false, 8, EH3_SB_WIDE7, EH3_RING, PT>),
                          dim3((unsigned)((span + ns7 - 1) / ns7), rows), dim3(512), 0, s, args...);
@@ -1202,9 +1304,9 @@ extern "C" int pcnerf_set_query_geometry(int geometry) {
 }
 
 extern "C" int pcnerf_set_train_query_form(int form) {
-  if (form != -1 && form != 0 && form != 2) {
-    pcn::set_error("pcnerf_set_train_query_form: train_query_form must be -1 (default), 0 (6 sample blocks) or 2 "
-                   "(7 sample blocks); 1 (half-skewed) is not built");
+  if (form != -1 && form != 0 && form != 2 && form != 4) {
+    pcn::set_error("pcnerf_set_train_query_form: train_query_form must be -1 (default), 0 (6 sample blocks), 2 "
+                   "(7 sample blocks) or 4 (8 sample blocks); 1 (half-skewed) and 3 are not built");
     return -2;
   }
   const int prev = pcn::g_train_query_form;

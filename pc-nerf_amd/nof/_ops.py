@@ -214,8 +214,9 @@ if os.environ.get("PCNERF_QUERY_GEOMETRY"):
 
 def set_train_query_form(form: int) -> int:
     """Form of the store-less train query in its 8-wave geometry (pcnerf_set_train_query_form): -1 the default
-    (form 2), 0 = 6 sample blocks (96 samples per workgroup), 2 = 7 sample blocks (112); 1 (half-skewed) is not
-    built.  Same bits in every form; for A/B timing and tests.  Returns the previous setting."""
+    (form 4), 0 = 6 sample blocks (96 samples per workgroup), 2 = 7 sample blocks (112), 4 = 8 sample blocks (128:
+    the CU's whole LDS, coefficients from L2); 1 (half-skewed) and 3 are not built.  Same bits in every form; for
+    A/B timing and tests.  Returns the previous setting."""
     prev = H.lib().pcnerf_set_train_query_form(int(form))
     if prev < -1:
         raise ValueError(H.lib().pcnerf_last_error().decode())
