@@ -545,6 +545,34 @@ int pcnerf_prof_read(int tag, double* total_ms, int64_t* launches, double* flops
  * TFLOP/s, *clock_mhz = median shader clock of the timed launches.  No reference counterpart (measurement only). */
 int pcnerf_mfma_ceiling(double seconds, double* tflops, double* clock_mhz, void* stream);
 
+/* ---------------------------------------------------------------- scan-to-field registration
+ * Replaces: render.py:13-36 (inference_val: embed, eval network, compositing) plus torch autograd of its depth to
+ * the ray origins and directions, and the normal equations a Gauss-Newton pose solver builds from them (no
+ * reference counterpart beyond autograd).  Argument errors of these entries return -1.
+ *
+ * pcnerf_render_depth_jac_fold: one render pass of a folded eval network (fold = pcnerf_nof_fold_eval's 64
+ *   doubles) in one launch, whatever pcnerf_set_eval_math selects: p = sigmoid(fl32(a . Embedding(o + d z) + c))
+ *   with pcnerf_nof_query_eval_fold's arithmetic (its bits), compositing (render.py:51-61, no noise) in float64
+ *   from that p, each output rounded once:
+ *   depth (n_rays), sumw (n_rays) = sum_s T_s p_s (unnormalised: the hit probability),
+ *   weights_or_null (n_rays, n_samples) = w / (sumw + eps), jac6_or_null (n_rays, 6) = d depth / d rays[:, 0:6]
+ *   with z constant: columns 0:3 sum_s g_s grad logit(x_s), 3:6 sum_s z_s g_s grad logit(x_s), g_s = d depth /
+ *   d logit_s (pcnerf_composite_backward's recurrence with dL/ddepth = 1).  1 <= n_samples <= 1024.
+ * pcnerf_gn_normal_eq: out30 (30 device doubles) = the upper triangle of H = sum w Jp^T Jp (21, row-major),
+ *   b = sum w Jp^T r (6), cost = sum rho(r), n_valid, one pad word, over the valid rays (sumw >= min_sumw, depth
+ *   finite, target finite and > 0).  r = depth - target; w = 1 for |r| <= huber_delta, else huber_delta / |r|
+ *   (huber_delta <= 0: plain least squares); Jp = [J_o, o x J_o + d x J_d] is the Jacobian of the left pose
+ *   perturbation T' = exp(xi) T, xi = (rho, phi), on the world-frame ray row (delta o = rho + phi x o,
+ *   delta d = phi x d).  `workspace` needs pcnerf_gn_workspace_bytes(n_rays) bytes.  float64 sums in a fixed
+ *   order, no atomics.  n_rays == 0 zeroes out30. */
+int pcnerf_render_depth_jac_fold(const float* rays, int64_t n_rays, int ray_stride, const float* z, int n_samples,
+                                 const double* fold, float eps, float* depth, float* sumw, float* weights_or_null,
+                                 float* jac6_or_null, void* stream);
+size_t pcnerf_gn_workspace_bytes(int64_t n_rays);
+int pcnerf_gn_normal_eq(const float* rays, int64_t n_rays, int ray_stride, const float* jac6, const float* depth,
+                        const float* sumw, const float* target, double huber_delta, double min_sumw,
+                        void* workspace, double* out30, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

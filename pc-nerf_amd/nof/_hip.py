@@ -156,6 +156,9 @@ _SIGS = {
                                                       ctypes.POINTER(NofGrads), vp]),
     "pcnerf_nof_forward_eval_param_backward": (c_int, [vp, i64, ctypes.POINTER(NofParams), c_float, vp, vp, vp,
                                                        c_size, ctypes.POINTER(NofGrads), vp]),
+    "pcnerf_render_depth_jac_fold": (c_int, [vp, i64, c_int, vp, c_int, vp, c_float, vp, vp, vp, vp, vp]),
+    "pcnerf_gn_workspace_bytes": (c_size, [i64]),
+    "pcnerf_gn_normal_eq": (c_int, [vp, i64, c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]),
 }
 
 

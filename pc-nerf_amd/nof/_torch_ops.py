@@ -35,6 +35,11 @@ def _need(op: str, name: str, t: Optional[Tensor], shape: tuple, dtype=torch.flo
     if t is None:
         return
     H.require_device(t)
+    _layout(op, name, t, shape, dtype)
+
+
+def _layout(op: str, name: str, t: Tensor, shape: tuple, dtype=torch.float32) -> None:
+    """_need's dtype / contiguity / shape part alone (wherever the tensor lives)."""
     if t.dtype != dtype or not t.is_contiguous():
         raise RuntimeError(f"pcnerf::{op}: {name} must be a contiguous {dtype} device tensor")
     ok = t.dim() == len(shape)
@@ -301,6 +306,77 @@ def _(rays, z, grad_logit, fold):
     return z.new_empty((z.shape[0], 6), dtype=torch.float32)
 
 
+# ----------------------------------------------------------------------------------------------- registration
+# One render pass of a folded eval network with its per-ray Jacobian, and the Gauss-Newton normal equations of a scan
+# (nof.registration).  Neither reads a process-wide selector: the pass is the fold whatever the eval math is.
+RENDER_JAC_MAX_SAMPLES = 1024   # one wave per ray, at most 16 samples per lane (pcnerf_render_depth_jac_fold)
+
+
+@torch.library.custom_op(f"{NS}::render_jac_fold", mutates_args=())
+def render_jac_fold(rays: Tensor, z: Tensor, fold: Tensor, eps: float, want_weights: bool,
+                    want_jac: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(depth (R,), sumw (R,), weights (R, S) or (0,), jac6 (R, 6) or (0,)) of one eval render pass (render.py:13-36
+    at noise_std = 0) of sigmoid(a . Embedding(o + d z) + c), fold = pcnerf::fold_eval: sumw is the unnormalised
+    weight sum (the hit probability), jac6 = d depth / d rays[:, 0:6] with z constant (what torch autograd of the
+    pass gives).  1 <= S <= 1024."""
+    op = "render_jac_fold"
+    _layout(op, "z", z, (None, ("min", 1)))
+    if z.shape[1] > RENDER_JAC_MAX_SAMPLES:
+        raise RuntimeError(f"pcnerf::{op}: z has {z.shape[1]} samples per ray, at most {RENDER_JAC_MAX_SAMPLES} "
+                           "are supported")
+    _layout(op, "rays", rays, (z.shape[0], ("min", 6)))
+    _layout(op, "fold", fold, (64,), torch.float64)
+    H.require_device(rays, z, fold)
+    _one_device(op, rays, z, fold)
+    R, S = z.shape
+    depth = torch.empty((R,), dtype=torch.float32, device=z.device)
+    sumw = torch.empty((R,), dtype=torch.float32, device=z.device)
+    w = torch.empty((R, S) if want_weights else (0,), dtype=torch.float32, device=z.device)
+    jac = torch.empty((R, 6) if want_jac else (0,), dtype=torch.float32, device=z.device)
+    H.check(H.lib().pcnerf_render_depth_jac_fold(rays.data_ptr(), R, rays.shape[1], z.data_ptr(), S, fold.data_ptr(),
+                                                 float(eps), depth.data_ptr(), sumw.data_ptr(),
+                                                 w.data_ptr() if want_weights else None,
+                                                 jac.data_ptr() if want_jac else None, H.stream_of(z)))
+    return depth, sumw, w, jac
+
+
+@render_jac_fold.register_fake
+def _(rays, z, fold, eps, want_weights, want_jac):
+    R, S = z.shape
+    return (z.new_empty((R,), dtype=torch.float32), z.new_empty((R,), dtype=torch.float32),
+            z.new_empty((R, S) if want_weights else (0,), dtype=torch.float32),
+            z.new_empty((R, 6) if want_jac else (0,), dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{NS}::gn_normal_eq", mutates_args=())
+def gn_normal_eq(rays: Tensor, jac6: Tensor, depth: Tensor, sumw: Tensor, target: Tensor, huber_delta: float,
+                 min_sumw: float) -> Tensor:
+    """(30,) float64: the upper triangle of H = sum w Jp^T Jp (21, row-major), b = sum w Jp^T r (6), the cost
+    sum rho(r), the number of valid rays and one pad word, for r = depth - target over the rays with sumw >= min_sumw
+    and finite depth and target > 0; Jp = [J_o, o x J_o + d x J_d] (left perturbation T' = exp(xi) T of the pose that
+    produced the world-frame rows); Huber weights, huber_delta <= 0: least squares (pcnerf_gn_normal_eq)."""
+    op = "gn_normal_eq"
+    _layout(op, "depth", depth, (None,))
+    R = depth.shape[0]
+    _layout(op, "rays", rays, (R, ("min", 6)))
+    _layout(op, "jac6", jac6, (R, 6))
+    _layout(op, "sumw", sumw, (R,))
+    _layout(op, "target", target, (R,))
+    H.require_device(rays, jac6, depth, sumw, target)
+    _one_device(op, rays, jac6, depth, sumw, target)
+    out = torch.empty((30,), dtype=torch.float64, device=depth.device)
+    ws = torch.empty((max(int(H.lib().pcnerf_gn_workspace_bytes(R)), 8),), dtype=torch.uint8, device=depth.device)
+    H.check(H.lib().pcnerf_gn_normal_eq(rays.data_ptr(), R, rays.shape[1], jac6.data_ptr(), depth.data_ptr(),
+                                        sumw.data_ptr(), target.data_ptr(), float(huber_delta), float(min_sumw),
+                                        ws.data_ptr(), out.data_ptr(), H.stream_of(depth)))
+    return out
+
+
+@gn_normal_eq.register_fake
+def _(rays, jac6, depth, sumw, target, huber_delta, min_sumw):
+    return depth.new_empty((30,), dtype=torch.float64)
+
+
 # ----------------------------------------------------------------------------------------------- frozen BatchNorm
 # Parameter gradients of the eval-mode network: logit = a(theta) . e + c(theta), so the gradients of a pass are those of
 # one pseudo-sample with input m = sum_s g_s e_s and constants scaled by s0 = sum_s g_s (include/pcnerf_hip.h).  The
@@ -517,4 +593,4 @@ def op_names() -> list:
     return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "query_points_eval", "composite",
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
             "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval", "eval_gmoments_rays",
-            "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads"]
+            "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads", "render_jac_fold", "gn_normal_eq"]
