@@ -573,6 +573,34 @@ int pcnerf_gn_normal_eq(const float* rays, int64_t n_rays, int ray_stride, const
                         const float* sumw, const float* target, double huber_delta, double min_sumw,
                         void* workspace, double* out30, void* stream);
 
+/* ---------------------------------------------------------------- pose-hypothesis scoring
+ * Replaces: per pose the rays of a scan (nof.registration.scan_rays), render.py:485-536 (render_rays_val at
+ * perturb = 0, noise_std = 0: coarse depths, coarse pass, sample_pdf with det = True, sort, fine pass) on two
+ * folded eval networks, and the cost sum of pcnerf_gn_normal_eq -- for n_poses poses in one launch plus a small
+ * reduction, with nothing per sample through memory (no reference counterpart for the batch: the observation model
+ * of Monte-Carlo localisation).  Argument errors return -1.
+ *
+ * pcnerf_score_poses_fold: points_sensor (n_beams, 3) float32, sensor frame; poses12 (n_poses, 12) float64 rows
+ *   [R row-major (9), t (3)], sensor -> world; parent_box6 = [lo (3), hi (3)] float64; fold_coarse / fold_fine =
+ *   pcnerf_nof_fold_eval's 64 doubles.  Per (pose, beam), in float64 and then cast once to float32: rng = |p|,
+ *   d = R (p / rng) renormalised, o = t, far = the exit from the box by the slab test (never below near).  The render
+ *   is pcnerf_sample_coarse, pcnerf_render_depth_jac_fold (weights), pcnerf_resample (u = NULL),
+ *   pcnerf_render_depth_jac_fold (depth, sumw) with their arithmetic.  r = depth - rng; a beam is usable when rng is
+ *   finite and > 0 and valid when usable, sumw >= min_sumw and depth finite; rho(r) = r^2 / 2, or
+ *   huber_delta (|r| - huber_delta / 2) for |r| > huber_delta > 0.
+ *   scores4 (n_poses, 4) float64 = [sum_valid rho(r), n_valid, sum_valid |r|, sum_usable sumw];
+ *   depth_or_null, sumw_or_null (n_poses, n_beams) float32, which do not change a bit of scores4.
+ *   3 <= n_samples, 1 <= n_importance, n_samples + n_importance <= 1024.  `workspace` needs
+ *   pcnerf_score_poses_workspace_bytes(n_poses, n_beams) bytes (32 per four beams of a pose).  float64 sums in an
+ *   order fixed by (n_poses, n_beams), no atomics: a pose scores the same bits alone or in a batch.
+ *   n_poses == 0 or n_beams == 0 zeroes scores4 and launches nothing else. */
+size_t pcnerf_score_poses_workspace_bytes(int64_t n_poses, int64_t n_beams);
+int pcnerf_score_poses_fold(const float* points_sensor, int64_t n_beams, const double* poses12, int64_t n_poses,
+                            const double* parent_box6, float near, int n_samples, int n_importance,
+                            const double* fold_coarse, const double* fold_fine, float eps, double huber_delta,
+                            double min_sumw, void* workspace, size_t workspace_bytes, double* scores4,
+                            float* depth_or_null, float* sumw_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

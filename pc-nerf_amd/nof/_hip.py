@@ -159,6 +159,9 @@ _SIGS = {
     "pcnerf_render_depth_jac_fold": (c_int, [vp, i64, c_int, vp, c_int, vp, c_float, vp, vp, vp, vp, vp]),
     "pcnerf_gn_workspace_bytes": (c_size, [i64]),
     "pcnerf_gn_normal_eq": (c_int, [vp, i64, c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]),
+    "pcnerf_score_poses_workspace_bytes": (c_size, [i64, i64]),
+    "pcnerf_score_poses_fold": (c_int, [vp, i64, vp, i64, vp, c_float, c_int, c_int, vp, vp, c_float, ctypes.c_double,
+                                        ctypes.c_double, vp, c_size, vp, vp, vp, vp]),
 }
 
 

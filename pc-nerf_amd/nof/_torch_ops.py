@@ -377,6 +377,66 @@ def _(rays, jac6, depth, sumw, target, huber_delta, min_sumw):
     return depth.new_empty((30,), dtype=torch.float64)
 
 
+# ----------------------------------------------------------------------------------------------- localisation
+# The whole two-pass render of a scan under many poses and the per-pose residual sums in one launch (nof.localization).
+# Reads no process-wide selector.
+SCORE_POSES_MIN_SAMPLES = 3        # the resampling needs one interior weight
+SCORE_POSES_MAX_SAMPLES = 1024     # N_samples + N_importance: one wave per beam, at most 16 samples per lane
+
+
+def check_score_samples(op: str, n_samples: int, n_importance: int) -> None:
+    if n_samples < SCORE_POSES_MIN_SAMPLES:
+        raise RuntimeError(f"pcnerf::{op}: N_samples = {n_samples}, at least {SCORE_POSES_MIN_SAMPLES} samples are "
+                           "needed")
+    if n_importance < 1:
+        raise RuntimeError(f"pcnerf::{op}: N_importance = {n_importance}, at least 1 sample is needed")
+    if n_samples + n_importance > SCORE_POSES_MAX_SAMPLES:
+        raise RuntimeError(f"pcnerf::{op}: N_samples + N_importance = {n_samples + n_importance} samples per beam, at "
+                           f"most {SCORE_POSES_MAX_SAMPLES} are supported")
+
+
+@torch.library.custom_op(f"{NS}::score_poses_fold", mutates_args=())
+def score_poses_fold(points: Tensor, poses12: Tensor, box6: Tensor, fold_coarse: Tensor, fold_fine: Tensor,
+                     near: float, n_samples: int, n_importance: int, eps: float, huber_delta: float,
+                     min_sumw: float, want_depth: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """(scores4 (P, 4) float64 = [sum_valid rho(r), n_valid, sum_valid |r|, sum_usable sumw], depth (P, R) or (0,),
+    sumw (P, R) or (0,)) of the scan points (R, 3) (sensor frame) under the poses12 (P, 12) rows [R row-major, t]
+    against the two folded networks inside the box6 = [lo, hi]: scan_rays + render_scan + the cost of gn_normal_eq
+    per pose, fused (pcnerf_score_poses_fold).  want_depth does not change a bit of scores4."""
+    op = "score_poses_fold"
+    _layout(op, "points", points, (None, 3))
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "box6", box6, (6,), torch.float64)
+    _layout(op, "fold_coarse", fold_coarse, (64,), torch.float64)
+    _layout(op, "fold_fine", fold_fine, (64,), torch.float64)
+    check_score_samples(op, n_samples, n_importance)
+    H.require_device(points, poses12, box6, fold_coarse, fold_fine)
+    _one_device(op, points, poses12, box6, fold_coarse, fold_fine)
+    R, Pn = points.shape[0], poses12.shape[0]
+    dev = points.device
+    scores = torch.empty((Pn, 4), dtype=torch.float64, device=dev)
+    depth = torch.empty((Pn, R) if want_depth else (0,), dtype=torch.float32, device=dev)
+    sumw = torch.empty((Pn, R) if want_depth else (0,), dtype=torch.float32, device=dev)
+    nbytes = int(H.lib().pcnerf_score_poses_workspace_bytes(Pn, R))
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+    H.check(H.lib().pcnerf_score_poses_fold(points.data_ptr(), R, poses12.data_ptr(), Pn, box6.data_ptr(),
+                                            float(near), int(n_samples), int(n_importance),
+                                            fold_coarse.data_ptr(), fold_fine.data_ptr(), float(eps),
+                                            float(huber_delta), float(min_sumw), ws.data_ptr(), nbytes,
+                                            scores.data_ptr(), depth.data_ptr() if want_depth else None,
+                                            sumw.data_ptr() if want_depth else None, H.stream_of(points)))
+    return scores, depth, sumw
+
+
+@score_poses_fold.register_fake
+def _(points, poses12, box6, fold_coarse, fold_fine, near, n_samples, n_importance, eps, huber_delta, min_sumw,
+      want_depth):
+    R, Pn = points.shape[0], poses12.shape[0]
+    return (points.new_empty((Pn, 4), dtype=torch.float64),
+            points.new_empty((Pn, R) if want_depth else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R) if want_depth else (0,), dtype=torch.float32))
+
+
 # ----------------------------------------------------------------------------------------------- frozen BatchNorm
 # Parameter gradients of the eval-mode network: logit = a(theta) . e + c(theta), so the gradients of a pass are those of
 # one pseudo-sample with input m = sum_s g_s e_s and constants scaled by s0 = sum_s g_s (include/pcnerf_hip.h).  The
@@ -593,4 +653,5 @@ def op_names() -> list:
     return ["embed", "sample_coarse", "perturb", "resample", "sample_pdf", "pack_eval", "query_eval", "query_points_eval", "composite",
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
             "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval", "eval_gmoments_rays",
-            "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads", "render_jac_fold", "gn_normal_eq"]
+            "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads", "render_jac_fold", "gn_normal_eq",
+            "score_poses_fold"]
