@@ -601,6 +601,66 @@ int pcnerf_score_poses_fold(const float* points_sensor, int64_t n_beams, const d
                             double min_sumw, void* workspace, size_t workspace_bytes, double* scores4,
                             float* depth_or_null, float* sumw_or_null, void* stream);
 
+/* ---------------------------------------------------------------- batched pose refinement
+ * Replaces: the loop of nof.registration.register_scan_fold (per evaluation scan_rays, render.py:485-536 at
+ * perturb = 0, noise_std = 0 on two folded eval networks with torch autograd of the fine depth to the ray,
+ * pcnerf_gn_normal_eq, a 30-double read-back and a host-side numpy solve and se3_exp) -- for n_poses poses at once,
+ * every step on the device and stream order the only synchronisation between evaluations (no reference counterpart
+ * for the batch: the refinement stage of Monte-Carlo localisation, multi-start registration).  Argument errors
+ * return -1 before anything is launched.
+ *
+ * The state of a pose is PCNERF_LM_STATE_DOUBLES = 64 doubles:
+ *   [ 0..11] T_acc    the last accepted pose, [R row-major (9), t (3)], sensor -> world
+ *   [12..23] T_trial  the pose the next evaluation renders
+ *   [24..53] the accepted evaluation's normal30 row (pcnerf_gn_normal_eq's out30 layout: 21 of H, 6 of b, cost,
+ *            n_valid, pad)
+ *   [54] lambda   [55] status   [56] evaluations made   [57] accepted evaluations   [58..63] the last xi
+ * status: 0 running, 1 converged (|xi| < xi_tol; T_trial includes that last step), 2 fewer than 6 valid beams (the
+ * pose is not determined), 3 a zero pivot or a non-finite xi in the solve (T_trial = T_acc).  A pose with
+ * status != 0 costs nothing further: its workgroups return at once and its state keeps every word.
+ *
+ * pcnerf_pose_normal_eq_fold: one evaluation of all running poses, pcnerf_score_poses_fold's operands and render
+ *   (the same bits of depth and sumw), the fine pass with pcnerf_render_depth_jac_fold's Jacobian path, then
+ *   pcnerf_gn_normal_eq's terms per beam on those float32 values and the float32 ray row.  The poses are the
+ *   states' T_trial, or poses12_or_null (n_poses, 12) when state_or_null is NULL.  normal30 (n_poses, 30) float64;
+ *   the row of a pose with status != 0 is zeroed.  depth_or_null, sumw_or_null (n_poses, n_beams) and jac6_or_null
+ *   (n_poses, n_beams, 6) float32 do not change a bit of normal30 (rows of stopped poses are not written).
+ *   3 <= n_samples, 1 <= n_importance, n_samples + n_importance <= 1024.  `workspace` needs
+ *   pcnerf_pose_normal_eq_workspace_bytes(n_poses, n_beams) bytes (256 per four beams of a pose).  float64 sums in
+ *   an order fixed by (n_poses, n_beams), no atomics.  n_poses == 0 launches nothing; n_beams == 0 zeroes normal30.
+ * pcnerf_lm_init: state (n_poses, 64) <- T_acc = T_trial = poses12, lambda = damping, everything else 0.
+ * pcnerf_lm_update: register_scan_fold's step for every running pose from its normal30 row, in float64: one more
+ *   evaluation; n_valid < 6 -> status 2 and nothing else moves; else the evaluation is accepted when none was
+ *   accepted yet or cost <= the accepted cost (lambda / 10 except on the first; a NaN cost is a rejection once
+ *   something is accepted), otherwise rejected (lambda x 10); (H + lambda diag H) xi = -b of the accepted evaluation
+ *   by elimination with partial pivoting; T_trial = se3_exp(xi) T_acc (nof.registration.se3_exp's branches and
+ *   series); |xi| < xi_tol -> status 1.  eval_costs_or_null (n_poses, iters) float64 and accepted_or_null (n_poses,
+ *   iters) uint8 receive the cost and the decision at column iter_index (0 <= iter_index < iters when given).
+ * pcnerf_refine_poses_fold: pcnerf_lm_init, then iters x (pcnerf_pose_normal_eq_fold on the states, pcnerf_lm_update),
+ *   enqueued on `stream` with no synchronisation.  Writes poses12_out (n_poses, 12) = T_trial, or T_acc for status
+ *   2 / 3; the state rows; normal30 (the last evaluation's rows, also scratch); eval_costs (NaN where not
+ *   evaluated) and accepted.
+ * pcnerf_se3_apply: poses12_out[p] = se3_exp(xi6[p]) poses12[p], xi = (rho, phi), float64 (the motion-model update
+ *   of a particle set). */
+#define PCNERF_LM_STATE_DOUBLES 64
+size_t pcnerf_pose_normal_eq_workspace_bytes(int64_t n_poses, int64_t n_beams);
+int pcnerf_pose_normal_eq_fold(const float* points_sensor, int64_t n_beams, const double* poses12_or_null,
+                               int64_t n_poses, const double* state_or_null, const double* parent_box6, float near,
+                               int n_samples, int n_importance, const double* fold_coarse, const double* fold_fine,
+                               float eps, double huber_delta, double min_sumw, void* workspace,
+                               size_t workspace_bytes, double* normal30, float* depth_or_null, float* sumw_or_null,
+                               float* jac6_or_null, void* stream);
+int pcnerf_lm_init(const double* poses12, int64_t n_poses, double damping, double* state, void* stream);
+int pcnerf_lm_update(const double* normal30, int64_t n_poses, double xi_tol, double* state,
+                     double* eval_costs_or_null, uint8_t* accepted_or_null, int iter_index, int iters, void* stream);
+int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_beams, const double* poses12, int64_t n_poses,
+                             const double* parent_box6, float near, int n_samples, int n_importance,
+                             const double* fold_coarse, const double* fold_fine, float eps, double huber_delta,
+                             double min_sumw, double damping, double xi_tol, int iters, void* workspace,
+                             size_t workspace_bytes, double* normal30, double* state, double* poses12_out,
+                             double* eval_costs, uint8_t* accepted, void* stream);
+int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, double* poses12_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,858 @@
+// Batched pose refinement against folded eval networks: damped Gauss-Newton (Levenberg-Marquardt) on the range
+// residuals of one scan for many poses at once, with no host synchronisation between evaluations.  An evaluation is
+// three launches in stream order:
+//
+//   k_pose_normal_eq_fold<MAXB>  k_score_poses_fold's layout (localize.hip): one wave per (pose, beam), four beams
+//                                per 256-thread workgroup, ceil(R / 4) workgroups per pose; folds, pose, box and loss
+//                                parameters through LDS; per wave an LDS slice zc (S) | draws (I) | weights + cdf,
+//                                aliased by the merged depths.  Steps 1-5 are that kernel's (the same arithmetic, the
+//                                same bits of depth and sumw); the fine pass also carries k_render_jac_fold's Jacobian
+//                                path (register.hip): the 30 sincosf of a sample feed the logit and grad logit, the
+//                                reverse affine recurrence gives g_s = d depth / d logit_s without a division by
+//                                1 - p, jac6 is per-lane float64 partials in sample order, wave_sum_d and one rounding
+//                                to float32.  Then k_gn_normal_eq's terms on those float32 values and the float32 ray
+//                                row: Jp = [J_o, o x J_o + d x J_d], r = depth - rng, the Huber weight, the validity
+//                                rule -> 21 of H's upper triangle, 6 of b, rho(r) and 1.  The four waves' terms are
+//                                added in wave order into one 32-double partial per workgroup.  The coarse pass
+//                                carries no Jacobian, and nothing per sample goes through memory.  A workgroup whose
+//                                pose has status != 0 (the state the previous launch wrote) returns before its first
+//                                barrier; the test is uniform across the workgroup.
+//   k_pose_normal_eq_sum         one workgroup per pose adds its ceil(R / 4) partials, eight chains (partials q,
+//                                q + 8, ...) and a fixed tree, into normal30[pose] (pcnerf_gn_normal_eq's out30); a
+//                                stopped pose's row is zeroed.
+//   k_lm_update                  one thread per pose, float64: nof.registration.register_scan_fold's state machine
+//                                (accept / reject, lambda / 10 or x 10, the 6 x 6 solve by elimination with partial
+//                                pivoting, T <- se3_exp(xi) T), kept fully in registers.
+//   k_se3_apply                  poses12_out[p] = se3_exp(xi[p]) poses12[p] with the same device function.
+// No atomics, every output word has one writer, and geometry and summation order depend on (P, R) alone: a pose
+// refines to the same bits alone or in a batch, with or without the per-beam outputs.  Loops are bounded by S and I
+// (the binary searches by their logarithm), never by data, and every LDS index is clamped, so NaN rays (rng == 0, a
+// non-finite point) cost time but cannot leave their slice; they are not counted.
+#include "pcnerf_internal.h"
+
+namespace pcn {
+
+constexpr int PN_MAX_S = 1024;   // 64 lanes x 16 samples per lane, the fine pass's S + I
+constexpr int PN_W = 32;         // doubles per partial: 21 + 6 + cost + n_valid, padded (normal30 rows hold 30)
+constexpr int LM_STATE = PCNERF_LM_STATE_DOUBLES;
+// the state's fields (include/pcnerf_hip.h)
+constexpr int LM_TACC = 0, LM_TTRIAL = 12, LM_N30 = 24, LM_LAMBDA = 54, LM_STATUS = 55, LM_EVALS = 56, LM_NACC = 57,
+              LM_XI = 58;
+
+__device__ __forceinline__ void pn_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// floats of one wave's LDS slice
+__host__ __device__ inline int pn_slice_floats(int S, int I) { return S + I + (2 * S > S + I ? 2 * S : S + I); }
+
+// The logit a . e(x) + c (k_nof_eval_fold's chains and summation order); GRAD: also its gradient to x
+// (logit_grad_pos's chains) from the same sincosf (register.hip's rj_logit_and_grad, localize.hip's sp_logit)
+template <bool GRAD>
+__device__ __forceinline__ double pn_logit(const float (&p)[3], const double* __restrict__ a, double (&g)[3]) {
+  double part[6];
+  double gs[3], gc[3];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    part[m] = a[m] * (double)p[m];
+    part[3 + m] = 0.0;
+    g[m] = a[m];
+    gs[m] = 0.0;
+    gc[m] = 0.0;
+  }
+#pragma unroll 2
+  for (int k = 0; k < 10; ++k) {
+    const float sc = (float)(1 << k);
+    const double dsc = (double)(1 << k);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      float sv, cv;
+      sincosf(sc * p[m], &sv, &cv);
+      part[m] += a[3 + 6 * k + m] * (double)sv;
+      part[3 + m] += a[6 + 6 * k + m] * (double)cv;
+      if constexpr (GRAD) {
+        gs[m] += (dsc * a[3 + 6 * k + m]) * (double)cv;   // d sin(2^k x)/dx = 2^k cos
+        gc[m] -= (dsc * a[6 + 6 * k + m]) * (double)sv;   // d cos(2^k x)/dx = -2^k sin
+      }
+    }
+  }
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) g[m] += gs[m] + gc[m];
+  }
+  double acc = a[63];
+  acc += ((part[0] + part[1]) + (part[2] + part[3])) + (part[4] + part[5]);
+  return acc;
+}
+
+__device__ __forceinline__ double pn_excl_prod(double v, int lane) {
+  double incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(incl, o, 64);
+    if (lane >= o) incl *= n;
+  }
+  const double ex = __shfl_up(incl, 1, 64);
+  return lane == 0 ? 1.0 : ex;
+}
+
+__device__ __forceinline__ double pn_excl_sum(double v, int lane) {
+  double incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += n;
+  }
+  const double ex = __shfl_up(incl, 1, 64);
+  return lane == 0 ? 0.0 : ex;
+}
+
+// U entering each lane's block from above: lanes l + 1 .. 63's affine maps (Y = A + Bm Y_next) composed, applied to 0
+__device__ __forceinline__ double pn_suffix_affine(double A, double Bm, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double An = __shfl_down(A, o, 64), Bn = __shfl_down(Bm, o, 64);
+    if (lane + o < 64) {
+      A = A + Bm * An;
+      Bm = Bm * Bn;
+    }
+  }
+  const double An1 = __shfl_down(A, 1, 64);
+  return lane == 63 ? 0.0 : An1;
+}
+
+// One render pass of the wave's ray over the n depths zs (LDS): k_render_jac_fold's forward and, JAC, its Jacobian
+// path.  Lane l owns the samples l B .. l B + B - 1, B = ceil(n / 64) <= MAXB.  w_out (LDS, n floats) or NULL;
+// jac (JAC): d depth / d (o, d), every lane the same six sums.
+template <int MAXB, bool JAC>
+__device__ __forceinline__ void pn_pass(const float (&row)[6], const float* zs, int n, const double* __restrict__ a,
+                                        float eps, int lane, float* w_out, double& dep, double& hit,
+                                        double (&jac)[6]) {
+  const int B = (n + 63) / 64;
+  const int i0 = lane * B;
+  const int nb = max(0, min(min(B, MAXB), n - i0));
+  // samples past the lane's block count as p = 0 at z = 0: factors of one and terms of zero everywhere below
+  float pv[MAXB], zv[MAXB];
+  double gx[JAC ? MAXB : 1][3];
+#pragma unroll
+  for (int j = 0; j < MAXB; ++j) {
+    pv[j] = 0.0f;
+    zv[j] = 0.0f;
+    if constexpr (JAC) gx[j][0] = gx[j][1] = gx[j][2] = 0.0;
+  }
+#pragma nounroll
+  for (int j = 0; j < nb; ++j) {   // a rolled loop (one copy of the 30 sincosf); the selects keep the indices static
+    const float z = zs[i0 + j];
+    float x[3];
+    sample_point(row, z, x);
+    double d[3];
+    const float ps = sigmoid_ref((float)pn_logit<JAC>(x, a, d));
+#pragma unroll
+    for (int jj = 0; jj < MAXB; ++jj) {
+      if (jj == j) {
+        pv[jj] = ps;
+        zv[jj] = z;
+        if constexpr (JAC) {
+          gx[jj][0] = d[0];
+          gx[jj][1] = d[1];
+          gx[jj][2] = d[2];
+        }
+      }
+    }
+  }
+  double loc = 1.0;
+#pragma unroll
+  for (int j = 0; j < MAXB; ++j) loc *= 1.0 - (double)pv[j];
+  double T = pn_excl_prod(loc, lane);
+  double wv[MAXB], tv[JAC ? MAXB : 1];
+  double sw = 0.0;
+#pragma unroll
+  for (int j = 0; j < MAXB; ++j) {
+    if constexpr (JAC) tv[j] = T;
+    wv[j] = T * (double)pv[j];
+    sw += wv[j];
+    T *= 1.0 - (double)pv[j];
+  }
+  hit = wave_sum_d(sw);
+  const double rden = 1.0 / (hit + (double)eps);
+  double sd = 0.0;
+#pragma unroll
+  for (int j = 0; j < MAXB; ++j) {
+    wv[j] = wv[j] * rden;
+    sd += wv[j] * (double)zv[j];
+  }
+  dep = wave_sum_d(sd);
+  if (w_out) {
+#pragma unroll
+    for (int j = 0; j < MAXB; ++j)
+      if (j < nb) w_out[i0 + j] = (float)wv[j];
+  }
+  if constexpr (JAC) {
+    // d depth / d logit_s (k_composite_bwd's recurrence with dL/ddepth = 1); wv is dead, its registers hold g
+#pragma unroll
+    for (int j = 0; j < MAXB; ++j) wv[j] = ((double)zv[j] - dep) * rden;   // d depth / d w~_j
+    double A = 0.0, Bm = 1.0;   // this lane's affine map U_end -> U_{i0 - 1}
+#pragma unroll
+    for (int j = MAXB - 1; j >= 0; --j) {
+      const double aj = wv[j] * (double)pv[j], bj = 1.0 - (double)pv[j];
+      A = aj + bj * A;
+      Bm = bj * Bm;
+    }
+    double U = pn_suffix_affine(A, Bm, lane);
+#pragma unroll
+    for (int j = MAXB - 1; j >= 0; --j) {
+      const double gp = tv[j] * (wv[j] - U);
+      U = wv[j] * (double)pv[j] + (1.0 - (double)pv[j]) * U;
+      wv[j] = gp * (1.0 - (double)pv[j]) * (double)pv[j];   // sigmoid backward: now d depth / d logit_j
+    }
+#pragma unroll
+    for (int m = 0; m < 6; ++m) jac[m] = 0.0;
+#pragma unroll
+    for (int j = 0; j < MAXB; ++j) {   // sample order
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        const double g = wv[j] * gx[j][m];
+        jac[m] += g;
+        jac[3 + m] += (double)zv[j] * g;
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 6; ++m) jac[m] = wave_sum_d(jac[m]);
+  }
+}
+
+// value a of cat(zc, fs)
+__device__ __forceinline__ float pn_cat(const float* zc, const float* fs, int S, int a) {
+  return a < S ? zc[a] : fs[a - S];
+}
+
+// k_resample at u == NULL and the merge with zc, on the wave's slice (localize.hip, step 4)
+__device__ __forceinline__ void pn_resample_merge(const float* zc, float* fs, const float* ws, float* cdf, float* zf,
+                                                  int S, int I, int lane) {
+  const int nbin = S - 1, npdf = nbin - 1;
+  const float* w = ws + 1;
+  const int B = (npdf + 63) / 64, i0 = lane * B;
+  double ls = 0.0;
+#pragma nounroll
+  for (int j = 0; j < B; ++j) {
+    const int i = i0 + j;
+    if (i < npdf) ls += (double)(w[i] + 1e-5f);
+  }
+  const float tot = (float)wave_sum_d(ls);
+  double lp = 0.0;
+#pragma nounroll
+  for (int j = 0; j < B; ++j) {
+    const int i = i0 + j;
+    if (i < npdf) lp += (double)((w[i] + 1e-5f) / tot);
+  }
+  double run = pn_excl_sum(lp, lane);
+  if (lane == 0) cdf[0] = 0.0f;
+#pragma nounroll
+  for (int j = 0; j < B; ++j) {
+    const int i = i0 + j;
+    if (i < npdf) {
+      run += (double)((w[i] + 1e-5f) / tot);
+      cdf[i + 1] = (float)run;
+    }
+  }
+  pn_wave_lds_sync();
+#pragma nounroll
+  for (int k = lane; k < I; k += 64) {
+    const float u = linspace01(k, I);
+    int lo = 0, hi = nbin;   // first index with cdf > u (searchsorted right=True)
+#pragma nounroll
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cdf[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    const int below = max(lo - 1, 0), above = max(min(lo, nbin - 1), 0);
+    const float c0 = cdf[below], c1 = cdf[above];
+    float denom = c1 - c0;
+    if (denom < 1e-5f) denom = 1.0f;
+    const float t = (u - c0) / denom;
+    const float b0 = 0.5f * (zc[below + 1] + zc[below]), b1 = 0.5f * (zc[above + 1] + zc[above]);
+    fs[k] = b0 + t * (b1 - b0);
+  }
+  pn_wave_lds_sync();   // (also orders the last ws / cdf read before zf's first write)
+  bool ok = true;
+#pragma nounroll
+  for (int i = lane; i < S; i += 64) ok = ok && (zc[i] == zc[i]) && (i + 1 >= S || zc[i] <= zc[i + 1]);
+#pragma nounroll
+  for (int k = lane; k < I; k += 64) ok = ok && (fs[k] == fs[k]) && (k + 1 >= I || fs[k] <= fs[k + 1]);
+  const int n = S + I;
+  if (__all(ok)) {
+#pragma nounroll
+    for (int i = lane; i < S; i += 64) {
+      const float v = zc[i];
+      int lo = 0, hi = I;
+#pragma nounroll
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (fs[mid] < v) lo = mid + 1; else hi = mid;
+      }
+      zf[min(i + lo, n - 1)] = v;
+    }
+#pragma nounroll
+    for (int k = lane; k < I; k += 64) {
+      const float v = fs[k];
+      int lo = 0, hi = S;
+#pragma nounroll
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (zc[mid] <= v) lo = mid + 1; else hi = mid;
+      }
+      zf[min(k + lo, n - 1)] = v;
+    }
+  } else {
+#pragma nounroll
+    for (int a = lane; a < n; a += 64) {
+      const float va = pn_cat(zc, fs, S, a);
+      const bool na = !(va == va);
+      int rank = 0;
+#pragma nounroll
+      for (int b = 0; b < n; ++b) {
+        const float vb = pn_cat(zc, fs, S, b);
+        const bool nb = !(vb == vb);
+        rank += (vb < va) || (na && !nb) || ((vb == va || (na && nb)) && b < a);   // NaNs after every number
+      }
+      zf[min(rank, n - 1)] = va;
+    }
+  }
+  pn_wave_lds_sync();
+}
+
+template <int MAXB>
+__global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
+    const float* __restrict__ points, int64_t n_beams, const double* __restrict__ poses12,
+    const double* __restrict__ state, int bpp, const double* __restrict__ box6, float near, int S, int I,
+    const double* __restrict__ fold_c, const double* __restrict__ fold_f, float eps, double delta_arg,
+    double min_sumw_arg, double* __restrict__ part, float* __restrict__ depth_out, float* __restrict__ sumw_out,
+    float* __restrict__ jac_out) {
+  extern __shared__ float pn_lds[];
+  __shared__ double fa[2][64];
+  __shared__ double red[4][PN_W];
+  __shared__ double pb[20];   // [R row-major (9), t (3), lo (3), hi (3), huber_delta, min_sumw]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t pose = blockIdx.x / (unsigned)bpp;
+  // a stopped pose costs nothing further (uniform across the workgroup, before the first barrier)
+  if (state && state[LM_STATE * pose + LM_STATUS] != 0.0) return;
+  const double* __restrict__ psrc = state ? state + LM_STATE * pose + LM_TTRIAL : poses12 + 12 * pose;
+  if (tid < 128) fa[tid >> 6][lane] = (tid < 64 ? fold_c : fold_f)[lane];
+  else if (tid < 140) pb[tid - 128] = psrc[tid - 128];
+  else if (tid < 146) pb[tid - 128] = box6[tid - 140];
+  else if (tid < 148) pb[tid - 128] = tid == 146 ? delta_arg : min_sumw_arg;
+  __syncthreads();
+  const int64_t beam = (int64_t)(blockIdx.x - (unsigned)pose * (unsigned)bpp) * 4 + wave;
+  double mine = 0.0;   // lane k < 29: term k of this wave's beam
+  if (beam < n_beams) {   // (wave-uniform: the shuffles below always have 64 lanes)
+    float* zc = pn_lds + (size_t)wave * pn_slice_floats(S, I);
+    float* fs = zc + S;
+    float* ws = fs + I;      // coarse weights (S)
+    float* cdf = ws + S;     // (S - 1)
+    float* zf = ws;          // the merged depths (S + I): ws and cdf are dead when it is written
+    // 1. the ray (every lane the same values)
+    const double* T = pb;
+    const double* box = pb + 12;
+    const float* __restrict__ pt = points + 3 * beam;
+    const double px = (double)pt[0], py = (double)pt[1], pz = (double)pt[2];
+    const double rng = sqrt((px * px + py * py) + pz * pz);
+    const double ux = px / rng, uy = py / rng, uz = pz / rng;
+    double d[3], o[3];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      d[m] = (T[3 * m] * ux + T[3 * m + 1] * uy) + T[3 * m + 2] * uz;
+      o[m] = T[9 + m];
+    }
+    const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    const double nan64 = __builtin_nan("");
+    double tmin = 0.0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      d[m] = d[m] / dn;
+      const double inv = 1.0 / d[m];
+      const double t1 = (box[m] - o[m]) * inv, t2 = (box[3 + m] - o[m]) * inv;
+      // torch.maximum / min propagate NaN; a NaN t2 counts as +inf
+      const double tm = t2 != t2 ? (double)INFINITY : (t1 != t1 ? nan64 : fmax(t1, t2));
+      tmin = m == 0 ? tm : ((tmin != tmin || tm != tm) ? nan64 : fmin(tmin, tm));
+    }
+    const double far64 = tmin != tmin ? tmin : fmax(tmin, (double)near);
+    float row[6];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      row[m] = (float)o[m];
+      row[3 + m] = (float)d[m];
+    }
+    const float far = (float)far64, target = (float)rng;
+    // 2. coarse depths
+#pragma nounroll
+    for (int i = lane; i < S; i += 64) zc[i] = lerp_z(near, far, linspace01(i, S));
+    pn_wave_lds_sync();
+    // 3. the coarse pass (no Jacobian), 4. resampling and the merge, 5. the fine pass with its Jacobian
+    double dep = 0.0, hit = 0.0, jac[6];
+    pn_pass<MAXB, false>(row, zc, S, fa[0], eps, lane, ws, dep, hit, jac);
+    pn_wave_lds_sync();
+    pn_resample_merge(zc, fs, ws, cdf, zf, S, I, lane);
+    pn_pass<MAXB, true>(row, zf, S + I, fa[1], eps, lane, nullptr, dep, hit, jac);
+    // 6. k_gn_normal_eq's terms, on the float32 values the composed route hands to it
+    const float dv = (float)dep, sv = (float)hit;
+    float jf[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) jf[m] = (float)jac[m];
+    const double delta = pb[18], min_sumw = pb[19];
+    const bool valid = (double)sv >= min_sumw && isfinite(dv) && isfinite(target) && target > 0.0f;
+    if (valid) {
+      double ro[3], rd[3], Jo[3], Jd[3], Jp[6];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        ro[m] = (double)row[m];
+        rd[m] = (double)row[3 + m];
+        Jo[m] = (double)jf[m];
+        Jd[m] = (double)jf[3 + m];
+        Jp[m] = Jo[m];
+      }
+      Jp[3] = (ro[1] * Jo[2] - ro[2] * Jo[1]) + (rd[1] * Jd[2] - rd[2] * Jd[1]);
+      Jp[4] = (ro[2] * Jo[0] - ro[0] * Jo[2]) + (rd[2] * Jd[0] - rd[0] * Jd[2]);
+      Jp[5] = (ro[0] * Jo[1] - ro[1] * Jo[0]) + (rd[0] * Jd[1] - rd[1] * Jd[0]);
+      const double res = (double)dv - (double)target, ar = fabs(res);
+      const bool lin = delta > 0.0 && ar > delta;   // Huber's linear branch; delta <= 0: plain least squares
+      const double w = lin ? delta / ar : 1.0;
+      int k = 0;
+#pragma unroll
+      for (int p = 0; p < 6; ++p) {
+        const double wj = w * Jp[p];
+#pragma unroll
+        for (int q = p; q < 6; ++q) {
+          if (lane == k) mine = wj * Jp[q];
+          ++k;
+        }
+        if (lane == 21 + p) mine = wj * res;
+      }
+      if (lane == 27) mine = lin ? delta * (ar - 0.5 * delta) : 0.5 * (res * res);
+      if (lane == 28) mine = 1.0;
+    }
+    if (lane == 0) {
+      const int64_t g = pose * n_beams + beam;
+      if (depth_out) depth_out[g] = dv;
+      if (sumw_out) sumw_out[g] = sv;
+      if (jac_out) {
+#pragma unroll
+        for (int m = 0; m < 6; ++m) jac_out[6 * g + m] = jf[m];
+      }
+    }
+  }
+  if (lane < PN_W) red[wave][lane] = mine;
+  __syncthreads();
+  if (tid < PN_W)
+    part[(int64_t)blockIdx.x * PN_W + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// normal30[p][f] = sum_w part[p bpp + w][f]: thread (f, q) adds partials q, q + 8, ... in order, the eight chains in a
+// fixed tree.  A stopped pose's row is zeroed (its partials were not written).
+__global__ __launch_bounds__(256) void k_pose_normal_eq_sum(const double* __restrict__ part, int bpp,
+                                                            const double* __restrict__ state,
+                                                            double* __restrict__ normal30) {
+  __shared__ double red[8][PN_W];
+  const int f = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const int64_t pose = blockIdx.x;
+  if (state && state[LM_STATE * pose + LM_STATUS] != 0.0) {   // (uniform across the workgroup)
+    if (threadIdx.x < 30) normal30[30 * pose + threadIdx.x] = 0.0;
+    return;
+  }
+  const double* __restrict__ pp = part + pose * bpp * PN_W;
+  double acc = 0.0;
+  for (int w = q; w < bpp; w += 8) acc += pp[(int64_t)w * PN_W + f];
+  red[q][f] = acc;
+  __syncthreads();
+  if (q == 0 && f < 30)
+    normal30[30 * pose + f] =
+        ((red[0][f] + red[1][f]) + (red[2][f] + red[3][f])) + ((red[4][f] + red[5][f]) + (red[6][f] + red[7][f]));
+}
+
+// ------------------------------------------------------------------------------------------------ SE(3), float64
+// sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3 without cancellation: nof.registration._abc's branches and series
+__device__ __forceinline__ void lm_abc(double theta, double& a, double& b, double& c) {
+  a = theta < 1e-8 ? 1.0 : sin(theta) / theta;
+  const double h = 0.5 * theta;
+  const double sh = h < 1e-8 ? 1.0 : sin(h) / h;
+  b = 0.5 * sh * sh;
+  if (theta < 0.5) {
+    const double t2 = theta * theta;
+    double term = 1.0 / 6.0;
+    c = 0.0;
+#pragma unroll
+    for (int k = 1; k < 9; ++k) {   // 1/3! - t^2/5! + t^4/7! - ...
+      c += term;
+      term *= -t2 / (double)((2 * k + 2) * (2 * k + 3));
+    }
+  } else {
+    c = (theta - sin(theta)) / (theta * theta * theta);
+  }
+}
+
+// out = se3_exp(xi) T on 12-double rows [R row-major (9), t (3)], xi = (rho, phi)
+__device__ __forceinline__ void lm_se3_exp_apply(const double (&xi)[6], const double (&T)[12], double (&out)[12]) {
+  const double x = xi[3], y = xi[4], z = xi[5];
+  const double theta = sqrt((x * x + y * y) + z * z);
+  double a, b, c;
+  lm_abc(theta, a, b, c);
+  const double K[3][3] = {{0.0, -z, y}, {z, 0.0, -x}, {-y, x, 0.0}};
+  double E[3][3], te[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double vr = 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+      const double eye = i == j ? 1.0 : 0.0;
+      E[i][j] = (eye + a * K[i][j]) + b * k2;
+      const double v = (eye + b * K[i][j]) + c * k2;
+      vr = j == 0 ? v * xi[0] : vr + v * xi[j];
+    }
+    te[i] = vr;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = (E[i][0] * T[j] + E[i][1] * T[3 + j]) + E[i][2] * T[6 + j];
+    out[9 + i] = ((E[i][0] * T[9] + E[i][1] * T[10]) + E[i][2] * T[11]) + te[i];
+  }
+}
+
+// xi of (H + lam diag H) xi = -b, H's upper triangle and b from a normal30 row: elimination with partial pivoting
+// (the first largest |entry| of the column, as LAPACK's), every index static.  false: a zero pivot or a non-finite xi.
+__device__ __forceinline__ bool lm_solve(const double* __restrict__ n30, double lam, double (&xi)[6]) {
+  double A[6][7];
+  {
+    int k = 0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+#pragma unroll
+      for (int q = p; q < 6; ++q) {
+        A[p][q] = n30[k];
+        A[q][p] = n30[k];
+        ++k;
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 6; ++p) {
+    A[p][p] = A[p][p] + lam * A[p][p];
+    A[p][6] = -n30[21 + p];
+  }
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    int piv = c;
+    double best = fabs(A[c][c]);
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      const double v = fabs(A[r][c]);
+      if (v > best) {
+        best = v;
+        piv = r;
+      }
+    }
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      if (r == piv) {
+#pragma unroll
+        for (int q = c; q < 7; ++q) {
+          const double t = A[c][q];
+          A[c][q] = A[r][q];
+          A[r][q] = t;
+        }
+      }
+    }
+    const double pv = A[c][c];
+    if (pv == 0.0) ok = false;
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      const double l = A[r][c] / pv;
+#pragma unroll
+      for (int q = c + 1; q < 7; ++q) A[r][q] -= l * A[c][q];
+    }
+  }
+#pragma unroll
+  for (int r = 5; r >= 0; --r) {
+    double s = A[r][6];
+#pragma unroll
+    for (int q = r + 1; q < 6; ++q) s -= A[r][q] * xi[q];
+    xi[r] = s / A[r][r];
+    ok = ok && isfinite(xi[r]);
+  }
+  return ok;
+}
+
+__global__ __launch_bounds__(64) void k_lm_init(const double* __restrict__ poses12, int64_t n_poses, double damping,
+                                                double* __restrict__ state) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;   // one thread per state word
+  if (i >= n_poses * LM_STATE) return;
+  const int64_t p = i / LM_STATE;
+  const int f = (int)(i - p * LM_STATE);
+  double v = 0.0;
+  if (f < LM_N30) v = poses12[12 * p + (f < 12 ? f : f - 12)];   // T_acc = T_trial = the start
+  else if (f == LM_LAMBDA) v = damping;
+  state[i] = v;
+}
+
+__global__ __launch_bounds__(64) void k_lm_records_init(int64_t n, double* __restrict__ eval_costs,
+                                                        uint8_t* __restrict__ accepted) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  if (eval_costs) eval_costs[i] = __builtin_nan("");
+  if (accepted) accepted[i] = 0;
+}
+
+// register_scan_fold's state machine for one evaluation of every running pose (one thread per pose)
+__global__ __launch_bounds__(64) void k_lm_update(const double* __restrict__ normal30, int64_t n_poses, double xi_tol,
+                                                  double* __restrict__ state, double* __restrict__ eval_costs,
+                                                  uint8_t* __restrict__ accepted, int iter_index, int iters) {
+  const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (p >= n_poses) return;
+  double* __restrict__ st = state + LM_STATE * p;
+  if (st[LM_STATUS] != 0.0) return;
+  const double* __restrict__ nq = normal30 + 30 * p;
+  const double cost = nq[27], n_valid = nq[28];
+  st[LM_EVALS] = st[LM_EVALS] + 1.0;
+  const bool rec = iter_index >= 0 && iter_index < iters;
+  if (rec && eval_costs) eval_costs[p * iters + iter_index] = cost;
+  if (!(n_valid >= 6.0)) {   // the pose is not determined
+    st[LM_STATUS] = 2.0;
+    return;
+  }
+  double lam = st[LM_LAMBDA];
+  const double nacc = st[LM_NACC];
+  if (nacc == 0.0 || cost <= st[LM_N30 + 27]) {   // (a NaN cost: a rejection once something is accepted)
+    if (nacc != 0.0) lam = lam / 10.0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) st[LM_TACC + k] = st[LM_TTRIAL + k];
+#pragma unroll
+    for (int k = 0; k < 30; ++k) st[LM_N30 + k] = nq[k];
+    st[LM_NACC] = nacc + 1.0;
+    if (rec && accepted) accepted[p * iters + iter_index] = 1;
+  } else {
+    lam = lam * 10.0;
+  }
+  st[LM_LAMBDA] = lam;
+  double xi[6], Ta[12], Tn[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Ta[k] = st[LM_TACC + k];
+  if (!lm_solve(st + LM_N30, lam, xi)) {   // the pose stays at the last accepted one
+    st[LM_STATUS] = 3.0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) st[LM_TTRIAL + k] = Ta[k];
+    return;
+  }
+  lm_se3_exp_apply(xi, Ta, Tn);
+  double n2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    st[LM_XI + k] = xi[k];
+    n2 += xi[k] * xi[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) st[LM_TTRIAL + k] = Tn[k];
+  if (sqrt(n2) < xi_tol) st[LM_STATUS] = 1.0;   // (the pose includes this last step)
+}
+
+// poses12_out = T_trial, or T_acc where the pose is undetermined or the solve failed
+__global__ __launch_bounds__(64) void k_lm_poses_out(const double* __restrict__ state, int64_t n_poses,
+                                                     double* __restrict__ poses12_out) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_poses * 12) return;
+  const int64_t p = i / 12;
+  const int f = (int)(i - p * 12);
+  const double* __restrict__ st = state + LM_STATE * p;
+  const double s = st[LM_STATUS];
+  poses12_out[i] = st[(s == 2.0 || s == 3.0 ? LM_TACC : LM_TTRIAL) + f];
+}
+
+__global__ __launch_bounds__(64) void k_se3_apply(const double* __restrict__ xi6, const double* __restrict__ poses12,
+                                                  int64_t n_poses, double* __restrict__ poses12_out) {
+  const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (p >= n_poses) return;
+  double xi[6], T[12], out[12];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) xi[k] = xi6[6 * p + k];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = poses12[12 * p + k];
+  lm_se3_exp_apply(xi, T, out);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) poses12_out[12 * p + k] = out[k];
+}
+
+inline int64_t pn_blocks_per_pose(int64_t n_beams) { return (n_beams + 3) / 4; }
+inline unsigned lm_blocks(int64_t n) { return (unsigned)((n + 63) / 64); }
+
+void pn_check_samples(const char* name, int n_samples, int n_importance) {
+  const std::string who(name);
+  PCN_CHECK(n_samples >= 3, who + ": n_samples < 3 (the resampling needs one interior weight)");
+  PCN_CHECK(n_importance >= 1, who + ": n_importance < 1");
+  PCN_CHECK((int64_t)n_samples + n_importance <= PN_MAX_S,
+            who + ": n_samples + n_importance > 1024 (one wave per beam, at most 16 samples per lane)");
+}
+
+size_t pn_workspace_bytes(int64_t n_poses, int64_t n_beams) {
+  if (n_poses <= 0 || n_beams <= 0) return 0;
+  return (size_t)n_poses * (size_t)pn_blocks_per_pose(n_beams) * PN_W * sizeof(double);
+}
+
+// every check an evaluation makes, before anything is launched (n_poses > 0)
+void pn_check_eval(const char* name, const float* points, int64_t n_beams, int64_t n_poses, const double* box6,
+                   const double* fold_c, const double* fold_f, void* workspace, size_t workspace_bytes) {
+  const std::string who(name);
+  if (n_beams == 0) return;
+  PCN_CHECK(points && box6 && fold_c && fold_f && workspace, who + ": null argument");
+  PCN_CHECK(workspace_bytes >= pn_workspace_bytes(n_poses, n_beams),
+            who + ": workspace smaller than pcnerf_pose_normal_eq_workspace_bytes");
+  const int64_t bpp = pn_blocks_per_pose(n_beams);
+  PCN_CHECK(bpp < (int64_t)1 << 31 && n_poses < (int64_t)1 << 31 && n_poses * bpp < (int64_t)1 << 31,
+            who + ": too many (pose, beam) pairs for one launch");
+}
+
+// one evaluation of all running poses (checked by pn_check_eval); n_poses > 0
+void pn_launch_eval(const float* points, int64_t n_beams, const double* poses12, int64_t n_poses, const double* state,
+                    const double* box6, float near, int S, int I, const double* fold_c, const double* fold_f,
+                    float eps, double delta, double min_sumw, void* workspace, double* normal30, float* depth,
+                    float* sumw, float* jac6, hipStream_t stream) {
+  if (n_beams == 0) {
+    PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), stream));
+    return;
+  }
+  const int64_t bpp = pn_blocks_per_pose(n_beams);
+  const size_t lds = (size_t)4 * pn_slice_floats(S, I) * sizeof(float);   // <= 48 KiB
+  const int B = (S + I + 63) / 64;
+  double* part = reinterpret_cast<double*>(workspace);
+#define PN_LAUNCH(MB)                                                                                          \
+  hipLaunchKernelGGL(k_pose_normal_eq_fold<MB>, dim3((unsigned)(n_poses * bpp)), dim3(256), lds, stream, points, \
+                     n_beams, poses12, state, (int)bpp, box6, near, S, I, fold_c, fold_f, eps, delta, min_sumw, \
+                     part, depth, sumw, jac6)
+  if (B <= 1) PN_LAUNCH(1);
+  else if (B <= 2) PN_LAUNCH(2);
+  else if (B <= 4) PN_LAUNCH(4);
+  else if (B <= 8) PN_LAUNCH(8);
+  else PN_LAUNCH(16);
+#undef PN_LAUNCH
+  hipLaunchKernelGGL(k_pose_normal_eq_sum, dim3((unsigned)n_poses), dim3(256), 0, stream, part, (int)bpp, state,
+                     normal30);
+}
+
+}  // namespace pcn
+
+using namespace pcn;
+
+// these entries report an argument error as -1 (the message in pcnerf_last_error)
+#define REF_API_END                                       \
+  return 0;                                               \
+  }                                                       \
+  catch (const std::exception& ex__) {                    \
+    pcn::set_error(ex__.what());                          \
+    return -1;                                            \
+  }
+
+extern "C" size_t pcnerf_pose_normal_eq_workspace_bytes(int64_t n_poses, int64_t n_beams) {
+  return pn_workspace_bytes(n_poses, n_beams);
+}
+
+extern "C" int pcnerf_pose_normal_eq_fold(const float* points_sensor, int64_t n_beams, const double* poses12_or_null,
+                                          int64_t n_poses, const double* state_or_null, const double* parent_box6,
+                                          float near, int n_samples, int n_importance, const double* fold_coarse,
+                                          const double* fold_fine, float eps, double huber_delta, double min_sumw,
+                                          void* workspace, size_t workspace_bytes, double* normal30,
+                                          float* depth_or_null, float* sumw_or_null, float* jac6_or_null,
+                                          void* stream) {
+  PCN_API_BEGIN
+  const char* who = "pcnerf_pose_normal_eq_fold";
+  PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_pose_normal_eq_fold: negative count");
+  pn_check_samples(who, n_samples, n_importance);
+  if (n_poses == 0) return 0;
+  PCN_CHECK(normal30 && (poses12_or_null || state_or_null), "pcnerf_pose_normal_eq_fold: null argument");
+  pn_check_eval(who, points_sensor, n_beams, n_poses, parent_box6, fold_coarse, fold_fine, workspace,
+                workspace_bytes);
+  pn_launch_eval(points_sensor, n_beams, poses12_or_null, n_poses, state_or_null, parent_box6, near, n_samples,
+                 n_importance, fold_coarse, fold_fine, eps, huber_delta, min_sumw, workspace, normal30, depth_or_null,
+                 sumw_or_null, jac6_or_null, (hipStream_t)stream);
+  PCN_LAUNCH_CHECK(who);
+  REF_API_END
+}
+
+extern "C" int pcnerf_lm_init(const double* poses12, int64_t n_poses, double damping, double* state, void* stream) {
+  PCN_API_BEGIN
+  PCN_CHECK(n_poses >= 0, "pcnerf_lm_init: negative count");
+  if (n_poses == 0) return 0;
+  PCN_CHECK(poses12 && state, "pcnerf_lm_init: null argument");
+  PCN_CHECK(n_poses < (int64_t)1 << 31, "pcnerf_lm_init: too many poses for one launch");
+  hipLaunchKernelGGL(k_lm_init, dim3(lm_blocks(n_poses * LM_STATE)), dim3(64), 0, (hipStream_t)stream, poses12,
+                     n_poses, damping, state);
+  PCN_LAUNCH_CHECK("pcnerf_lm_init");
+  REF_API_END
+}
+
+extern "C" int pcnerf_lm_update(const double* normal30, int64_t n_poses, double xi_tol, double* state,
+                                double* eval_costs_or_null, uint8_t* accepted_or_null, int iter_index, int iters,
+                                void* stream) {
+  PCN_API_BEGIN
+  PCN_CHECK(n_poses >= 0, "pcnerf_lm_update: negative count");
+  if (eval_costs_or_null || accepted_or_null)
+    PCN_CHECK(iter_index >= 0 && iter_index < iters, "pcnerf_lm_update: iter_index outside [0, iters)");
+  if (n_poses == 0) return 0;
+  PCN_CHECK(normal30 && state, "pcnerf_lm_update: null argument");
+  PCN_CHECK(n_poses < (int64_t)1 << 31, "pcnerf_lm_update: too many poses for one launch");
+  hipLaunchKernelGGL(k_lm_update, dim3(lm_blocks(n_poses)), dim3(64), 0, (hipStream_t)stream, normal30, n_poses,
+                     xi_tol, state, eval_costs_or_null, accepted_or_null, iter_index, iters);
+  PCN_LAUNCH_CHECK("pcnerf_lm_update");
+  REF_API_END
+}
+
+extern "C" int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_beams, const double* poses12,
+                                        int64_t n_poses, const double* parent_box6, float near, int n_samples,
+                                        int n_importance, const double* fold_coarse, const double* fold_fine,
+                                        float eps, double huber_delta, double min_sumw, double damping, double xi_tol,
+                                        int iters, void* workspace, size_t workspace_bytes, double* normal30,
+                                        double* state, double* poses12_out, double* eval_costs, uint8_t* accepted,
+                                        void* stream) {
+  PCN_API_BEGIN
+  const char* who = "pcnerf_refine_poses_fold";
+  PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_refine_poses_fold: negative count");
+  PCN_CHECK(iters >= 0, "pcnerf_refine_poses_fold: iters < 0");
+  pn_check_samples(who, n_samples, n_importance);
+  if (n_poses == 0) return 0;
+  PCN_CHECK(poses12 && normal30 && state && poses12_out, "pcnerf_refine_poses_fold: null argument");
+  PCN_CHECK(iters == 0 || (eval_costs && accepted), "pcnerf_refine_poses_fold: null argument");
+  PCN_CHECK(n_poses < (int64_t)1 << 31 && n_poses * ((int64_t)iters + LM_STATE) < (int64_t)1 << 37,
+            "pcnerf_refine_poses_fold: too many poses for one launch");   // (one thread per state / record word)
+  pn_check_eval(who, points_sensor, n_beams, n_poses, parent_box6, fold_coarse, fold_fine, workspace,
+                workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_lm_init, dim3(lm_blocks(n_poses * LM_STATE)), dim3(64), 0, s, poses12, n_poses, damping,
+                     state);
+  PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), s));
+  if (iters > 0)
+    hipLaunchKernelGGL(k_lm_records_init, dim3(lm_blocks(n_poses * iters)), dim3(64), 0, s, n_poses * iters,
+                       eval_costs, accepted);
+  for (int it = 0; it < iters; ++it) {   // stream order is the only synchronisation between evaluations
+    pn_launch_eval(points_sensor, n_beams, nullptr, n_poses, state, parent_box6, near, n_samples, n_importance,
+                   fold_coarse, fold_fine, eps, huber_delta, min_sumw, workspace, normal30, nullptr, nullptr, nullptr,
+                   s);
+    hipLaunchKernelGGL(k_lm_update, dim3(lm_blocks(n_poses)), dim3(64), 0, s, normal30, n_poses, xi_tol, state,
+                       eval_costs, accepted, it, iters);
+  }
+  hipLaunchKernelGGL(k_lm_poses_out, dim3(lm_blocks(n_poses * 12)), dim3(64), 0, s, state, n_poses, poses12_out);
+  PCN_LAUNCH_CHECK(who);
+  REF_API_END
+}
+
+extern "C" int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, double* poses12_out,
+                                void* stream) {
+  PCN_API_BEGIN
+  PCN_CHECK(n_poses >= 0, "pcnerf_se3_apply: negative count");
+  if (n_poses == 0) return 0;
+  PCN_CHECK(xi6 && poses12 && poses12_out, "pcnerf_se3_apply: null argument");
+  PCN_CHECK(n_poses < (int64_t)1 << 31, "pcnerf_se3_apply: too many poses for one launch");
+  hipLaunchKernelGGL(k_se3_apply, dim3(lm_blocks(n_poses)), dim3(64), 0, (hipStream_t)stream, xi6, poses12, n_poses,
+                     poses12_out);
+  PCN_LAUNCH_CHECK("pcnerf_se3_apply");
+  REF_API_END
+}

@@ -162,6 +162,15 @@ _SIGS = {
     "pcnerf_score_poses_workspace_bytes": (c_size, [i64, i64]),
     "pcnerf_score_poses_fold": (c_int, [vp, i64, vp, i64, vp, c_float, c_int, c_int, vp, vp, c_float, ctypes.c_double,
                                         ctypes.c_double, vp, c_size, vp, vp, vp, vp]),
+    "pcnerf_pose_normal_eq_workspace_bytes": (c_size, [i64, i64]),
+    "pcnerf_pose_normal_eq_fold": (c_int, [vp, i64, vp, i64, vp, vp, c_float, c_int, c_int, vp, vp, c_float,
+                                           ctypes.c_double, ctypes.c_double, vp, c_size, vp, vp, vp, vp, vp]),
+    "pcnerf_lm_init": (c_int, [vp, i64, ctypes.c_double, vp, vp]),
+    "pcnerf_lm_update": (c_int, [vp, i64, ctypes.c_double, vp, vp, vp, c_int, c_int, vp]),
+    "pcnerf_refine_poses_fold": (c_int, [vp, i64, vp, i64, vp, c_float, c_int, c_int, vp, vp, c_float,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
+                                         vp, c_size, vp, vp, vp, vp, vp, vp]),
+    "pcnerf_se3_apply": (c_int, [vp, vp, i64, vp, vp]),
 }
 
 

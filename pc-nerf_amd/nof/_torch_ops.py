@@ -654,4 +654,179 @@ def op_names() -> list:
             "composite_extras", "child_losses", "view_rows", "view_walk", "pointwise_loss",
             "pointwise_loss_backward", "fold_eval", "points_grad_eval", "rays_grad_eval", "eval_gmoments_rays",
             "eval_gmoments_points", "eval_gmoments_embedded", "eval_param_grads", "render_jac_fold", "gn_normal_eq",
-            "score_poses_fold"]
+            "score_poses_fold", "pose_normal_eq_fold", "lm_init", "lm_update", "refine_poses_fold", "se3_apply"]
+
+
+# ----------------------------------------------------------------------------------------------- batched refinement
+# Device-resident Levenberg-Marquardt over many poses (nof.registration.refine_poses_fold): one fused evaluation of all
+# running poses, the per-pose state machine and the SE(3) update as operators.  Reads no process-wide selector.
+LM_STATE_DOUBLES = 64   # PCNERF_LM_STATE_DOUBLES: T_acc 12 | T_trial 12 | normal30 30 | lambda, status, evals, accepted | xi 6
+
+
+def _ws(nbytes: int, dev) -> Tensor:
+    return torch.empty((max(int(nbytes), 8),), dtype=torch.uint8, device=dev)
+
+
+@torch.library.custom_op(f"{NS}::pose_normal_eq_fold", mutates_args=())
+def pose_normal_eq_fold(points: Tensor, poses12: Optional[Tensor], state: Optional[Tensor], box6: Tensor,
+                        fold_coarse: Tensor, fold_fine: Tensor, near: float, n_samples: int, n_importance: int,
+                        eps: float, huber_delta: float, min_sumw: float,
+                        want_beams: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(normal30 (P, 30) float64 in gn_normal_eq's layout, depth (P, R), sumw (P, R), jac6 (P, R, 6) float32 or (0,)
+    each) of one Gauss-Newton evaluation of the scan points (R, 3) under P poses: the states' T_trial (state (P, 64),
+    lm_init / lm_update; poses with status != 0 are skipped: zero rows) or, without a state, the poses12 (P, 12) rows.
+    scan_rays + render_scan(want_jac) + gn_normal_eq per pose, fused (pcnerf_pose_normal_eq_fold).  want_beams does
+    not change a bit of normal30."""
+    op = "pose_normal_eq_fold"
+    _layout(op, "points", points, (None, 3))
+    if state is None and poses12 is None:
+        raise RuntimeError(f"pcnerf::{op}: one of poses12 and state is needed")
+    if state is not None:
+        _layout(op, "state", state, (None, LM_STATE_DOUBLES), torch.float64)
+    else:
+        _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "box6", box6, (6,), torch.float64)
+    _layout(op, "fold_coarse", fold_coarse, (64,), torch.float64)
+    _layout(op, "fold_fine", fold_fine, (64,), torch.float64)
+    check_score_samples(op, n_samples, n_importance)
+    src = state if state is not None else poses12
+    H.require_device(points, src, box6, fold_coarse, fold_fine)
+    _one_device(op, points, src, box6, fold_coarse, fold_fine)
+    R, Pn = points.shape[0], src.shape[0]
+    dev = points.device
+    n30 = torch.zeros((Pn, 30), dtype=torch.float64, device=dev)
+    depth = torch.zeros((Pn, R) if want_beams else (0,), dtype=torch.float32, device=dev)
+    sumw = torch.zeros((Pn, R) if want_beams else (0,), dtype=torch.float32, device=dev)
+    jac = torch.zeros((Pn, R, 6) if want_beams else (0,), dtype=torch.float32, device=dev)
+    nbytes = int(H.lib().pcnerf_pose_normal_eq_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_pose_normal_eq_fold(points.data_ptr(), R, None if state is not None else poses12.data_ptr(),
+                                               Pn, state.data_ptr() if state is not None else None, box6.data_ptr(),
+                                               float(near), int(n_samples), int(n_importance),
+                                               fold_coarse.data_ptr(), fold_fine.data_ptr(), float(eps),
+                                               float(huber_delta), float(min_sumw), ws.data_ptr(), nbytes,
+                                               n30.data_ptr(), depth.data_ptr() if want_beams else None,
+                                               sumw.data_ptr() if want_beams else None,
+                                               jac.data_ptr() if want_beams else None, H.stream_of(points)))
+    return n30, depth, sumw, jac
+
+
+@pose_normal_eq_fold.register_fake
+def _(points, poses12, state, box6, fold_coarse, fold_fine, near, n_samples, n_importance, eps, huber_delta, min_sumw,
+      want_beams):
+    R, Pn = points.shape[0], (state if state is not None else poses12).shape[0]
+    return (points.new_empty((Pn, 30), dtype=torch.float64),
+            points.new_empty((Pn, R) if want_beams else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R) if want_beams else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R, 6) if want_beams else (0,), dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{NS}::lm_init", mutates_args=())
+def lm_init(poses12: Tensor, damping: float) -> Tensor:
+    """state (P, 64) float64 of a refinement that starts at the poses12 (P, 12) rows: T_acc = T_trial = the start,
+    lambda = damping, status, counters and xi zero (pcnerf_lm_init)."""
+    op = "lm_init"
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    H.require_device(poses12)
+    state = torch.empty((poses12.shape[0], LM_STATE_DOUBLES), dtype=torch.float64, device=poses12.device)
+    H.check(H.lib().pcnerf_lm_init(poses12.data_ptr(), poses12.shape[0], float(damping), state.data_ptr(),
+                                   H.stream_of(poses12)))
+    return state
+
+
+@lm_init.register_fake
+def _(poses12, damping):
+    return poses12.new_empty((poses12.shape[0], LM_STATE_DOUBLES), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{NS}::lm_update", mutates_args=())
+def lm_update(normal30: Tensor, state: Tensor, xi_tol: float) -> tuple[Tensor, Tensor, Tensor]:
+    """(state' (P, 64), cost (P,) float64: the evaluation's cost, NaN for a pose that was not running, accepted (P,)
+    uint8) of one Levenberg-Marquardt step of every running pose from its normal30 row: register_scan_fold's accept /
+    reject rule, the damped 6 x 6 solve and T_trial = se3_exp(xi) T_acc in float64 (pcnerf_lm_update).  The input
+    state is not modified."""
+    op = "lm_update"
+    _layout(op, "state", state, (None, LM_STATE_DOUBLES), torch.float64)
+    _layout(op, "normal30", normal30, (state.shape[0], 30), torch.float64)
+    H.require_device(normal30, state)
+    _one_device(op, normal30, state)
+    Pn = state.shape[0]
+    out = state.clone()
+    cost = torch.full((Pn,), float("nan"), dtype=torch.float64, device=state.device)
+    acc = torch.zeros((Pn,), dtype=torch.uint8, device=state.device)
+    H.check(H.lib().pcnerf_lm_update(normal30.data_ptr(), Pn, float(xi_tol), out.data_ptr(), cost.data_ptr(),
+                                     acc.data_ptr(), 0, 1, H.stream_of(state)))
+    return out, cost, acc
+
+
+@lm_update.register_fake
+def _(normal30, state, xi_tol):
+    Pn = state.shape[0]
+    return (state.new_empty((Pn, LM_STATE_DOUBLES), dtype=torch.float64),
+            state.new_empty((Pn,), dtype=torch.float64), state.new_empty((Pn,), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{NS}::refine_poses_fold", mutates_args=())
+def refine_poses_fold(points: Tensor, poses12: Tensor, box6: Tensor, fold_coarse: Tensor, fold_fine: Tensor,
+                      near: float, n_samples: int, n_importance: int, eps: float, huber_delta: float,
+                      min_sumw: float, damping: float, xi_tol: float,
+                      iters: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(poses12_out (P, 12) float64, state (P, 64) float64, eval_costs (P, iters) float64 with NaN where a pose was
+    not evaluated, accepted (P, iters) uint8) of lm_init and iters x (pose_normal_eq_fold, lm_update), enqueued without
+    a host synchronisation (pcnerf_refine_poses_fold).  poses12_out is T_trial, or T_acc where status is 2 or 3."""
+    op = "refine_poses_fold"
+    _layout(op, "points", points, (None, 3))
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "box6", box6, (6,), torch.float64)
+    _layout(op, "fold_coarse", fold_coarse, (64,), torch.float64)
+    _layout(op, "fold_fine", fold_fine, (64,), torch.float64)
+    check_score_samples(op, n_samples, n_importance)
+    if iters < 0:
+        raise RuntimeError(f"pcnerf::{op}: iters = {iters} is negative")
+    H.require_device(points, poses12, box6, fold_coarse, fold_fine)
+    _one_device(op, points, poses12, box6, fold_coarse, fold_fine)
+    R, Pn = points.shape[0], poses12.shape[0]
+    dev = points.device
+    out = torch.zeros((Pn, 12), dtype=torch.float64, device=dev)
+    state = torch.zeros((Pn, LM_STATE_DOUBLES), dtype=torch.float64, device=dev)
+    costs = torch.full((Pn, iters), float("nan"), dtype=torch.float64, device=dev)
+    acc = torch.zeros((Pn, iters), dtype=torch.uint8, device=dev)
+    n30 = torch.empty((max(Pn, 1), 30), dtype=torch.float64, device=dev)
+    nbytes = int(H.lib().pcnerf_pose_normal_eq_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_refine_poses_fold(points.data_ptr(), R, poses12.data_ptr(), Pn, box6.data_ptr(),
+                                             float(near), int(n_samples), int(n_importance),
+                                             fold_coarse.data_ptr(), fold_fine.data_ptr(), float(eps),
+                                             float(huber_delta), float(min_sumw), float(damping), float(xi_tol),
+                                             int(iters), ws.data_ptr(), nbytes, n30.data_ptr(), state.data_ptr(),
+                                             out.data_ptr(), costs.data_ptr(), acc.data_ptr(), H.stream_of(points)))
+    return out, state, costs, acc
+
+
+@refine_poses_fold.register_fake
+def _(points, poses12, box6, fold_coarse, fold_fine, near, n_samples, n_importance, eps, huber_delta, min_sumw,
+      damping, xi_tol, iters):
+    Pn = poses12.shape[0]
+    return (points.new_empty((Pn, 12), dtype=torch.float64),
+            points.new_empty((Pn, LM_STATE_DOUBLES), dtype=torch.float64),
+            points.new_empty((Pn, iters), dtype=torch.float64), points.new_empty((Pn, iters), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{NS}::se3_apply", mutates_args=())
+def se3_apply(xi6: Tensor, poses12: Tensor) -> Tensor:
+    """(P, 12) float64 rows of se3_exp(xi6[p]) @ T[p], xi = (rho, phi), on the poses12 (P, 12) rows [R row-major, t]
+    (pcnerf_se3_apply: nof.registration.se3_exp's branches and series on the device)."""
+    op = "se3_apply"
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "xi6", xi6, (poses12.shape[0], 6), torch.float64)
+    H.require_device(xi6, poses12)
+    _one_device(op, xi6, poses12)
+    out = torch.empty_like(poses12)
+    H.check(H.lib().pcnerf_se3_apply(xi6.data_ptr(), poses12.data_ptr(), poses12.shape[0], out.data_ptr(),
+                                     H.stream_of(poses12)))
+    return out
+
+
+@se3_apply.register_fake
+def _(xi6, poses12):
+    return poses12.new_empty(tuple(poses12.shape), dtype=torch.float64)

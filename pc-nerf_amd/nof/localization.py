@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _torch_ops
-from .registration import EPSILON, _check_frozen, register_scan_fold, se3_exp
+from .registration import (EPSILON, RegistrationResult, _check_frozen, refine_poses_fold, register_scan_fold,
+                           se3_exp)
 
 P = torch.ops.pcnerf
 
@@ -145,7 +146,8 @@ def pose_distance(A, B):
 def localize_scan_fold(fold_c: torch.Tensor, fold_f: torch.Tensor, points_sensor: torch.Tensor, poses, parent_lo,
                        parent_hi, *, top_k: int = 4, miss_cost: Optional[float] = None, refine_iters: int = 20,
                        same_basin_tol=(1e-3, 1e-3), N_samples: int = 64, N_importance: int = 128,
-                       huber_delta: float = 0.0, min_sumw: float = 0.5, near: float = 0.05) -> LocalizationResult:
+                       huber_delta: float = 0.0, min_sumw: float = 0.5, near: float = 0.05,
+                       refine: str = "sequential") -> LocalizationResult:
     """localize_scan on the two folded networks.
 
     Every hypothesis p gets the mean cost ``score_p = (cost_p + miss_cost (n_usable - n_valid_p)) / n_usable`` over the
@@ -159,7 +161,14 @@ def localize_scan_fold(fold_c: torch.Tensor, fold_f: torch.Tensor, points_sensor
     radians) of an earlier (better-scored) candidate's found that candidate's basin again: it is returned in
     ``refined`` but does not compete, and the basin is credited to the better hypothesis.  The default, 1 mm and
     1 mrad, is far above what 20 evaluations leave of a start inside the basin (some 1e-5) and far below the spacing
-    of any useful hypothesis set."""
+    of any useful hypothesis set.
+
+    ``refine``: "sequential" refines the candidates one after the other with ``register_scan_fold`` (a host round trip
+    per evaluation); "batched" refines them in one ``refine_poses_fold`` call (no host synchronisation between
+    evaluations) and applies the same winner rule.  There a candidate left with fewer than 6 valid beams or a singular
+    solve (status 2 or 3) does not compete instead of raising; if none is left, RuntimeError."""
+    if refine not in ("sequential", "batched"):
+        raise ValueError(f"localize_scan: refine must be 'sequential' or 'batched'; got {refine!r}")
     kw = dict(N_samples=N_samples, N_importance=N_importance, huber_delta=huber_delta, min_sumw=min_sumw, near=near)
     T = torch.as_tensor(poses, dtype=torch.float64).detach()
     s = score_poses_fold(fold_c, fold_f, points_sensor, T, parent_lo, parent_hi, **kw)
@@ -174,6 +183,9 @@ def localize_scan_fold(fold_c: torch.Tensor, fold_f: torch.Tensor, points_sensor
     order = np.argsort(scores.cpu().numpy(), kind="stable")[:max(1, int(top_k))]
     T_host = T.cpu()
     refined, best = [], None
+    if refine == "batched":
+        return _localize_batched(fold_c, fold_f, points_sensor, T_host, order, parent_lo, parent_hi, int(refine_iters),
+                                 same_basin_tol, mc, n_usable, scores, kw)
     for i in order:
         res = register_scan_fold(fold_c, fold_f, points_sensor, T_host[int(i)], parent_lo, parent_hi,
                                  iters=int(refine_iters), **kw)
@@ -186,13 +198,40 @@ def localize_scan_fold(fold_c: torch.Tensor, fold_f: torch.Tensor, points_sensor
     return LocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined)
 
 
+def _localize_batched(fold_c, fold_f, points_sensor, T_host, order, parent_lo, parent_hi, refine_iters,
+                      same_basin_tol, mc, n_usable, scores, kw) -> LocalizationResult:
+    """The refinement stage of localize_scan_fold with all candidates in one refine_poses_fold call; one read-back at
+    the end, then the sequential path's winner rule on the host."""
+    idx = torch.as_tensor(np.asarray(order, dtype=np.int64))
+    r = refine_poses_fold(fold_c, fold_f, points_sensor, T_host[idx], parent_lo, parent_hi, iters=refine_iters, **kw)
+    poses, status = r.poses.cpu(), r.status.cpu().tolist()
+    n_valid, iterations = r.n_valid.cpu().tolist(), r.iterations.cpu().tolist()
+    eval_costs, mask = r.eval_costs.cpu(), r.accepted_mask.cpu()
+    refined, best = [], None
+    for k, i in enumerate(order):
+        costs = eval_costs[k][mask[k]].tolist()
+        res = RegistrationResult(poses[k], costs, int(n_valid[k]), int(iterations[k]), status[k] == 1)
+        again = any(dt <= same_basin_tol[0] and dr <= same_basin_tol[1]
+                    for dt, dr in (pose_distance(res.pose, q.pose) for q in refined))
+        refined.append(res)
+        if status[k] in (2, 3) or not costs:
+            continue
+        final = (costs[-1] + mc * (n_usable - res.n_valid)) / n_usable
+        if best is None or (not again and final < best[0]):
+            best = (final, int(i), res)
+    if best is None:
+        raise RuntimeError("localize_scan: no candidate is left after the refinement (fewer than 6 valid beams or a "
+                           "singular solve for each)")
+    return LocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined)
+
+
 def localize_scan(model_coarse, model_fine, points_sensor: torch.Tensor, poses, parent_lo, parent_hi, *,
                   top_k: int = 4, miss_cost: Optional[float] = None, refine_iters: int = 20,
                   **render_kw) -> LocalizationResult:
     """The pose of the scan ``points_sensor`` (R, 3, sensor frame, on the device) among the hypotheses ``poses``
     (P, 4, 4, sensor -> world) against the frozen eval-mode networks of a parent block: score all, refine the
     ``top_k`` best, return the best basin (localize_scan_fold).  ``render_kw``: N_samples, N_importance, huber_delta,
-    min_sumw, near."""
+    min_sumw, near, and refine ("sequential", the default, or "batched": localize_scan_fold)."""
     fold_c, fold_f = _folds(model_coarse, model_fine)
     return localize_scan_fold(fold_c, fold_f, points_sensor, poses, parent_lo, parent_hi, top_k=top_k,
                               miss_cost=miss_cost, refine_iters=refine_iters, **render_kw)

@@ -236,3 +236,95 @@ def register_scan(model_coarse, model_fine, points_sensor: torch.Tensor, init_po
     return register_scan_fold(fold_c, fold_f, points_sensor, init_pose, parent_lo, parent_hi, N_samples=N_samples,
                               N_importance=N_importance, iters=iters, huber_delta=huber_delta, min_sumw=min_sumw,
                               damping=damping, near=near, xi_tol=xi_tol)
+
+
+# ----------------------------------------------------------------------------------------------- many poses at once
+class RefineResult(NamedTuple):
+    poses: torch.Tensor          # (P, 4, 4) float64, device: T_trial, or the last accepted pose where status is 2 / 3
+    cost: torch.Tensor           # (P,) float64: the last accepted evaluation's cost (0 when none was accepted)
+    n_valid: torch.Tensor        # (P,) int64: its valid beams
+    iterations: torch.Tensor     # (P,) int64: evaluations made
+    accepted: torch.Tensor       # (P,) int64: evaluations accepted
+    status: torch.Tensor         # (P,) int64: 0 ran all iterations, 1 |xi| < xi_tol, 2 fewer than 6 valid beams,
+    #                              3 the damped normal equations were singular
+    eval_costs: torch.Tensor     # (P, iters) float64: every evaluation's cost, NaN where the pose had stopped
+    accepted_mask: torch.Tensor  # (P, iters) bool
+    lam: torch.Tensor            # (P,) float64: the final damping factor
+    state: torch.Tensor          # (P, 64) float64: the solver's state rows (include/pcnerf_hip.h)
+
+
+def _pose_rows(poses, device) -> torch.Tensor:
+    """(P, 4, 4) poses, host or device -> (P, 12) float64 device rows [R row-major, t] (copies only: the same bits
+    from either side)."""
+    T = torch.as_tensor(poses, dtype=torch.float64).detach()
+    if T.dim() != 3 or tuple(T.shape[1:]) != (4, 4):
+        raise RuntimeError(f"poses must be (P, 4, 4); got {tuple(T.shape)}")
+    return torch.cat([T[:, :3, :3].reshape(-1, 9), T[:, :3, 3]], -1).to(device).contiguous()
+
+
+def _rows_to_poses(rows: torch.Tensor) -> torch.Tensor:
+    """(P, 12) rows -> (P, 4, 4) on the rows' device (copies only)."""
+    T = torch.zeros((rows.shape[0], 4, 4), dtype=torch.float64, device=rows.device)
+    T[:, :3, :3] = rows[:, :9].reshape(-1, 3, 3)
+    T[:, :3, 3] = rows[:, 9:12]
+    T[:, 3, 3] = 1.0
+    return T
+
+
+def refine_poses_fold(fold_c: torch.Tensor, fold_f: torch.Tensor, points_sensor: torch.Tensor, poses, parent_lo,
+                      parent_hi, *, N_samples: int = 64, N_importance: int = 128, iters: int = 20,
+                      huber_delta: float = 0.0, min_sumw: float = 0.5, damping: float = 1e-6, near: float = 0.05,
+                      xi_tol: float = 1e-9) -> RefineResult:
+    """register_scan_fold's iteration for the P poses ``poses`` (P, 4, 4 float64, sensor -> world, host or device) of
+    one scan at once, entirely on the device (``torch.ops.pcnerf.refine_poses_fold``): per evaluation one fused launch
+    renders every running pose's scan with its Jacobian and forms the normal-equation terms, a small reduction adds
+    them per pose, and a small kernel runs the accept / reject rule, the damped 6 x 6 solve and
+    ``T <- se3_exp(xi) T`` per pose in float64.  Nothing is read back between evaluations; a pose that has stopped
+    (converged, undetermined or singular: ``status``) costs nothing further.  Every pose follows register_scan_fold's
+    branches, but where that raises for fewer than 6 valid beams this records status 2 and returns the start (or the
+    last accepted pose).  A pose refines to the same bits alone or in a batch.  3 <= N_samples, 1 <= N_importance,
+    N_samples + N_importance <= 1024."""
+    if not points_sensor.is_cuda:
+        raise RuntimeError("nof.registration renders device-resident scans; move points_sensor with .to('cuda') -- "
+                           "there is no CPU path")
+    if points_sensor.dim() != 2 or points_sensor.shape[1] != 3:
+        raise RuntimeError(f"points_sensor must be (R, 3); got {tuple(points_sensor.shape)}")
+    _torch_ops.check_score_samples("refine_poses_fold", int(N_samples), int(N_importance))
+    dev = points_sensor.device
+    box = torch.as_tensor(np.concatenate([np.asarray(parent_lo, dtype=np.float64).reshape(3),
+                                          np.asarray(parent_hi, dtype=np.float64).reshape(3)])).to(dev)
+    pts = points_sensor.detach().float().contiguous()
+    rows, state, costs, acc = P.refine_poses_fold(pts, _pose_rows(poses, dev), box, fold_c, fold_f, float(near),
+                                                  int(N_samples), int(N_importance), EPSILON, float(huber_delta),
+                                                  float(min_sumw), float(damping), float(xi_tol), int(iters))
+    as_int = lambda c: state[:, c].round().to(torch.int64)   # noqa: E731
+    return RefineResult(_rows_to_poses(rows), state[:, 24 + 27].clone(), as_int(24 + 28), as_int(56), as_int(57),
+                        as_int(55), costs, acc.bool(), state[:, 54].clone(), state)
+
+
+def refine_poses(model_coarse, model_fine, points_sensor: torch.Tensor, poses, parent_lo, parent_hi,
+                 **kw) -> RefineResult:
+    """refine_poses_fold on the frozen eval-mode networks of a parent block: their folds are composed once
+    (pcnerf::fold_eval).  A train-mode module and parameters that require grad raise, as in register_scan."""
+    _check_frozen(model_coarse, "model_coarse")
+    _check_frozen(model_fine, "model_fine")
+    if not points_sensor.is_cuda:
+        raise RuntimeError("nof.registration renders device-resident scans; move points_sensor with .to('cuda') -- "
+                           "there is no CPU path")
+    with torch.no_grad():
+        fold_c = P.fold_eval(_torch_ops.eval_params(model_coarse))
+        fold_f = P.fold_eval(_torch_ops.eval_params(model_fine))
+    return refine_poses_fold(fold_c, fold_f, points_sensor, poses, parent_lo, parent_hi, **kw)
+
+
+def apply_twists(poses: torch.Tensor, xi: torch.Tensor) -> torch.Tensor:
+    """(P, 4, 4) float64 ``se3_exp(xi[p]) @ poses[p]`` on the device (``torch.ops.pcnerf.se3_apply``): the left
+    perturbation of every pose by its own twist xi = (rho, phi), e.g. the motion-model update of a particle set.
+    ``poses`` (P, 4, 4) and ``xi`` (P, 6) are device tensors."""
+    if not (torch.is_tensor(poses) and poses.is_cuda and torch.is_tensor(xi) and xi.is_cuda):
+        raise RuntimeError("nof.registration.apply_twists takes device tensors -- there is no CPU path")
+    rows = _pose_rows(poses, poses.device)
+    x = xi.detach().to(torch.float64).contiguous()
+    if x.dim() != 2 or tuple(x.shape) != (rows.shape[0], 6):
+        raise RuntimeError(f"xi must be (P, 6) with P = {rows.shape[0]}; got {tuple(x.shape)}")
+    return _rows_to_poses(P.se3_apply(x, rows))
