@@ -48,6 +48,49 @@ __device__ __forceinline__ float wave_max_f(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// Exclusive multiplicative / additive scan of one double per lane across the wave.
+__device__ __forceinline__ double wave_excl_prod(double v, int lane) {
+  double incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(incl, o, 64);
+    if (lane >= o) incl *= n;
+  }
+  const double ex = __shfl_up(incl, 1, 64);
+  return lane == 0 ? 1.0 : ex;
+}
+__device__ __forceinline__ double wave_excl_sum(double v, int lane) {
+  double incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double n = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += n;
+  }
+  const double ex = __shfl_up(incl, 1, 64);
+  return lane == 0 ? 0.0 : ex;
+}
+// U entering each lane's block from above: lanes l + 1 .. 63's affine maps (Y = A + Bm Y_next) composed, applied to 0.
+// (render.hip's Grp<G>::suffix_affine keeps its own copy of the loop: it carries Y across the waves of G = 256 and
+// returns An1 + Bn1 Y, and calling this loop from there moved k_composite_bwd<64, 64>'s register allocation.)
+__device__ __forceinline__ double wave_suffix_affine(double A, double Bm, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double An = __shfl_down(A, o, 64), Bn = __shfl_down(Bm, o, 64);
+    if (lane + o < 64) {
+      A = A + Bm * An;
+      Bm = Bm * Bn;
+    }
+  }
+  const double An1 = __shfl_down(A, 1, 64);
+  return lane == 63 ? 0.0 : An1;
+}
+// Orders one wave's LDS writes before its reads of the same wave-private region (and the reads before the next
+// writes): no workgroup barrier, so the waves of a workgroup run out of phase.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // max |alpha(n) W[n][k]| over one layer's out_f x in_f weights by the whole block of NT threads (16-byte loads, eight
 // in flight per thread: two or three rounds for a 256 x 256..319 layer; fmaxf drops NaN weights, in any order)

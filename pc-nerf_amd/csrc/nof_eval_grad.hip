@@ -20,27 +20,7 @@ namespace pcn {
 
 // dlogit/dx at p: 30 sincosf (encode_full's arguments) and three 21-term float64 dots against a (LDS)
 __device__ __forceinline__ void logit_grad_pos(const float (&p)[3], const double* __restrict__ a, double (&g)[3]) {
-  double gs[3], gc[3];   // the sin and the cos columns' chains, per coordinate
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    g[m] = a[m];
-    gs[m] = 0.0;
-    gc[m] = 0.0;
-  }
-#pragma unroll 2
-  for (int k = 0; k < 10; ++k) {   // partly rolled, as k_nof_eval_fold: the coefficients stay in LDS
-    const float sc = (float)(1 << k);
-    const double dsc = (double)(1 << k);
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      float sv, cv;
-      sincosf(sc * p[m], &sv, &cv);
-      gs[m] += (dsc * a[3 + 6 * k + m]) * (double)cv;   // d sin(2^k x)/dx = 2^k cos
-      gc[m] -= (dsc * a[6 + 6 * k + m]) * (double)sv;   // d cos(2^k x)/dx = -2^k sin
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < 3; ++m) g[m] += gs[m] + gc[m];
+  fold_dot<false, true>(p, a, g);
 }
 
 __global__ __launch_bounds__(256) void k_points_grad_eval(const float* __restrict__ pts, int64_t n,

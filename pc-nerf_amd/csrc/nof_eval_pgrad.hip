@@ -25,12 +25,6 @@ namespace pcn {
 
 constexpr int GM_MAX_WG = 1024;   // workgroups of the moments pass (4 waves, one 64-sample tile per wave at a time)
 
-__device__ __forceinline__ void pg_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 inline int64_t gm_tiles(int64_t n) { return (n + 63) / 64; }
 inline int gm_workgroups(int64_t n) {
   const int64_t w = (gm_tiles(n) + 3) / 4;
@@ -89,10 +83,10 @@ __global__ __launch_bounds__(256) void k_eval_gmoments(const float* __restrict__
     }
     my[lane * 65 + 63] = 1.0f;
     gs[wave][lane] = ok ? pg_logit_grad(g, p, i) : 0.0f;   // a tail lane's row counts with g = 0
-    pg_wave_lds_sync();
+    wave_lds_sync();
 #pragma unroll 16
     for (int s = 0; s < 64; ++s) acc += (double)gs[wave][s] * (double)my[s * 65 + lane];
-    pg_wave_lds_sync();
+    wave_lds_sync();
   }
   red[wave][lane] = acc;
   __syncthreads();

@@ -151,13 +151,8 @@ __device__ __forceinline__ int64_t chunk_len(const SampleSrc& q, int64_t c) {
 // operand reads (16 bytes: 8 samples of one feature) of 16 lanes hit 16 disjoint bank groups.
 typedef _Float16 tf_f16x8 __attribute__((ext_vector_type(8)));
 
-// orders one wave's LDS writes before its reads of the same tile (and the reads before the next tile's writes):
-// the tiles are wave-private, so no workgroup barrier is needed and the four waves run out of phase
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// wave_lds_sync (common.h) orders one wave's LDS writes before its reads of the same tile (and the reads before the
+// next tile's writes): the tiles are wave-private, so no workgroup barrier is needed and the four waves run out of phase
 constexpr int TM_P = 72;
 
 template <bool PT = false>

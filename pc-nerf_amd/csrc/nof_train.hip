@@ -1073,12 +1073,6 @@ __device__ __forceinline__ float enc_feat1(const float (&p)[3], int f) {
   return f < 3 ? pf : f >= 63 ? 0.0f : fr < 3 ? sn : cs;
 }
 
-__device__ __forceinline__ void gram_lds_sync() {   // wave-private tiles: order one wave's LDS writes and reads
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(256, 2) void k_enc_gram(const float* __restrict__ rays, int stride,
                                                      const float* __restrict__ z, int S, int64_t c0,
                                                      const float* __restrict__ ein, int64_t n,
@@ -1151,7 +1145,7 @@ __global__ __launch_bounds__(256, 2) void k_enc_gram(const float* __restrict__ r
     }
     hi[63 * GR_P + lane] = ok ? (_Float16)dsc : (_Float16)0.0f;
     mi[63 * GR_P + lane] = (_Float16)0.0f;
-    gram_lds_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int o = (lane & 31) * GR_P + 16 * ks + 8 * (lane >> 5);
@@ -1177,7 +1171,7 @@ __global__ __launch_bounds__(256, 2) void k_enc_gram(const float* __restrict__ r
       d11[r] += (double)a11[r] * usc;
       a00[r] = a01[r] = a11[r] = 0.0f;
     }
-    gram_lds_sync();
+    wave_lds_sync();
   }
   // the four waves' partials summed in a fixed order through LDS (aliasing the tiles), one coalesced store
   __syncthreads();

@@ -113,6 +113,52 @@ __device__ __forceinline__ void encode_full(const float (&p)[3], float (&f)[64])
   f[63] = 0.0f;
 }
 
+// The folded eval network's logit is a . e(x) + c (a: 63 doubles, then c).  fold_dot is a . e(x)
+// straight from encode_full's sincosf, one per encoding pair.  VAL: the value, six independent float64 chains (sin /
+// cos per coordinate) summed at the end in a fixed order; without it 0 is returned.  GRAD: g = d logit / dx from the
+// same sincosf, since d sin(2^k x)/dx = 2^k cos(2^k x); without it g is not written.  The frequency loop is partly
+// rolled: the coefficients stay where a points (LDS), not in 126 registers.
+template <bool VAL, bool GRAD>
+__device__ __forceinline__ double fold_dot(const float (&p)[3], const double* __restrict__ a, double (&g)[3]) {
+  double part[6];
+  double gs[3], gc[3];   // the sin and the cos columns' chains, per coordinate
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    if constexpr (VAL) {
+      part[m] = a[m] * (double)p[m];
+      part[3 + m] = 0.0;
+    }
+    if constexpr (GRAD) {
+      g[m] = a[m];
+      gs[m] = 0.0;
+      gc[m] = 0.0;
+    }
+  }
+#pragma unroll 2
+  for (int k = 0; k < 10; ++k) {
+    const float sc = (float)(1 << k);
+    const double dsc = (double)(1 << k);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      float sv, cv;
+      sincosf(sc * p[m], &sv, &cv);
+      if constexpr (VAL) {
+        part[m] += a[3 + 6 * k + m] * (double)sv;
+        part[3 + m] += a[6 + 6 * k + m] * (double)cv;
+      }
+      if constexpr (GRAD) {
+        gs[m] += (dsc * a[3 + 6 * k + m]) * (double)cv;   // d sin(2^k x)/dx = 2^k cos
+        gc[m] -= (dsc * a[6 + 6 * k + m]) * (double)sv;   // d cos(2^k x)/dx = -2^k sin
+      }
+    }
+  }
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int m = 0; m < 3; ++m) g[m] += gs[m] + gc[m];
+  }
+  if constexpr (VAL) return ((part[0] + part[1]) + (part[2] + part[3])) + (part[4] + part[5]);
+  else return 0.0;
+}
 template <int MAP = 0>
 __device__ __forceinline__ void encode_half(const float (&p)[3], int h, float (&e)[32]) {
   float f[64];
@@ -143,6 +189,14 @@ __device__ __forceinline__ void load_embedding(const float* __restrict__ row, in
   catch (const std::exception& ex__) {                    \
     pcn::set_error(ex__.what());                          \
     return 1;                                             \
+  }
+// the same for the entries that report an argument error as -1 (the message in pcnerf_last_error)
+#define PCN_API_END_NEG                                   \
+  return 0;                                               \
+  }                                                       \
+  catch (const std::exception& ex__) {                    \
+    pcn::set_error(ex__.what());                          \
+    return -1;                                            \
   }
 #define PCN_CHECK(cond, msg)                              \
   do {                                                    \

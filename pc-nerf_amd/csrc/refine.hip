@@ -5,18 +5,15 @@
 //   k_pose_normal_eq_fold<MAXB>  k_score_poses_fold's layout (localize.hip): one wave per (pose, beam), four beams
 //                                per 256-thread workgroup, ceil(R / 4) workgroups per pose; folds, pose, box and loss
 //                                parameters through LDS; per wave an LDS slice zc (S) | draws (I) | weights + cdf,
-//                                aliased by the merged depths.  Steps 1-5 are that kernel's (the same arithmetic, the
-//                                same bits of depth and sumw); the fine pass also carries k_render_jac_fold's Jacobian
-//                                path (register.hip): the 30 sincosf of a sample feed the logit and grad logit, the
-//                                reverse affine recurrence gives g_s = d depth / d logit_s without a division by
-//                                1 - p, jac6 is per-lane float64 partials in sample order, wave_sum_d and one rounding
-//                                to float32.  Then k_gn_normal_eq's terms on those float32 values and the float32 ray
-//                                row: Jp = [J_o, o x J_o + d x J_d], r = depth - rng, the Huber weight, the validity
-//                                rule -> 21 of H's upper triangle, 6 of b, rho(r) and 1.  The four waves' terms are
-//                                added in wave order into one 32-double partial per workgroup.  The coarse pass
-//                                carries no Jacobian, and nothing per sample goes through memory.  A workgroup whose
-//                                pose has status != 0 (the state the previous launch wrote) returns before its first
-//                                barrier; the test is uniform across the workgroup.
+//                                aliased by the merged depths.  Steps 1-5 are fold_render.h's, the same bits of depth
+//                                and sumw as that kernel's; here two instantiations of the pass: the coarse one
+//                                carries no Jacobian, the fine one k_render_jac_fold's (register.hip).  Then
+//                                k_gn_normal_eq's terms on the float32 depth, sumw, jac6 and ray row, one term per
+//                                lane: 21 of H's upper triangle, 6 of b, rho(r) and 1.  The four waves' terms are
+//                                added in wave order into one 32-double partial per workgroup.  Nothing per sample
+//                                goes through memory.  A workgroup whose pose has status != 0 (the state the previous
+//                                launch wrote) returns before its first barrier; the test is uniform across the
+//                                workgroup.
 //   k_pose_normal_eq_sum         one workgroup per pose adds its ceil(R / 4) partials, eight chains (partials q,
 //                                q + 8, ...) and a fixed tree, into normal30[pose] (pcnerf_gn_normal_eq's out30); a
 //                                stopped pose's row is zeroed.
@@ -25,303 +22,16 @@
 //                                pivoting, T <- se3_exp(xi) T), kept fully in registers.
 //   k_se3_apply                  poses12_out[p] = se3_exp(xi[p]) poses12[p] with the same device function.
 // No atomics, every output word has one writer, and geometry and summation order depend on (P, R) alone: a pose
-// refines to the same bits alone or in a batch, with or without the per-beam outputs.  Loops are bounded by S and I
-// (the binary searches by their logarithm), never by data, and every LDS index is clamped, so NaN rays (rng == 0, a
-// non-finite point) cost time but cannot leave their slice; they are not counted.
-#include "pcnerf_internal.h"
+// refines to the same bits alone or in a batch, with or without the per-beam outputs.  NaN rays are not counted.
+#include "fold_render.h"
 
 namespace pcn {
 
-constexpr int PN_MAX_S = 1024;   // 64 lanes x 16 samples per lane, the fine pass's S + I
 constexpr int PN_W = 32;         // doubles per partial: 21 + 6 + cost + n_valid, padded (normal30 rows hold 30)
 constexpr int LM_STATE = PCNERF_LM_STATE_DOUBLES;
 // the state's fields (include/pcnerf_hip.h)
 constexpr int LM_TACC = 0, LM_TTRIAL = 12, LM_N30 = 24, LM_LAMBDA = 54, LM_STATUS = 55, LM_EVALS = 56, LM_NACC = 57,
               LM_XI = 58;
-
-__device__ __forceinline__ void pn_wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// floats of one wave's LDS slice
-__host__ __device__ inline int pn_slice_floats(int S, int I) { return S + I + (2 * S > S + I ? 2 * S : S + I); }
-
-// The logit a . e(x) + c (k_nof_eval_fold's chains and summation order); GRAD: also its gradient to x
-// (logit_grad_pos's chains) from the same sincosf (register.hip's rj_logit_and_grad, localize.hip's sp_logit)
-template <bool GRAD>
-__device__ __forceinline__ double pn_logit(const float (&p)[3], const double* __restrict__ a, double (&g)[3]) {
-  double part[6];
-  double gs[3], gc[3];
-#pragma unroll
-  for (int m = 0; m < 3; ++m) {
-    part[m] = a[m] * (double)p[m];
-    part[3 + m] = 0.0;
-    g[m] = a[m];
-    gs[m] = 0.0;
-    gc[m] = 0.0;
-  }
-#pragma unroll 2
-  for (int k = 0; k < 10; ++k) {
-    const float sc = (float)(1 << k);
-    const double dsc = (double)(1 << k);
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      float sv, cv;
-      sincosf(sc * p[m], &sv, &cv);
-      part[m] += a[3 + 6 * k + m] * (double)sv;
-      part[3 + m] += a[6 + 6 * k + m] * (double)cv;
-      if constexpr (GRAD) {
-        gs[m] += (dsc * a[3 + 6 * k + m]) * (double)cv;   // d sin(2^k x)/dx = 2^k cos
-        gc[m] -= (dsc * a[6 + 6 * k + m]) * (double)sv;   // d cos(2^k x)/dx = -2^k sin
-      }
-    }
-  }
-  if constexpr (GRAD) {
-#pragma unroll
-    for (int m = 0; m < 3; ++m) g[m] += gs[m] + gc[m];
-  }
-  double acc = a[63];
-  acc += ((part[0] + part[1]) + (part[2] + part[3])) + (part[4] + part[5]);
-  return acc;
-}
-
-__device__ __forceinline__ double pn_excl_prod(double v, int lane) {
-  double incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(incl, o, 64);
-    if (lane >= o) incl *= n;
-  }
-  const double ex = __shfl_up(incl, 1, 64);
-  return lane == 0 ? 1.0 : ex;
-}
-
-__device__ __forceinline__ double pn_excl_sum(double v, int lane) {
-  double incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += n;
-  }
-  const double ex = __shfl_up(incl, 1, 64);
-  return lane == 0 ? 0.0 : ex;
-}
-
-// U entering each lane's block from above: lanes l + 1 .. 63's affine maps (Y = A + Bm Y_next) composed, applied to 0
-__device__ __forceinline__ double pn_suffix_affine(double A, double Bm, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double An = __shfl_down(A, o, 64), Bn = __shfl_down(Bm, o, 64);
-    if (lane + o < 64) {
-      A = A + Bm * An;
-      Bm = Bm * Bn;
-    }
-  }
-  const double An1 = __shfl_down(A, 1, 64);
-  return lane == 63 ? 0.0 : An1;
-}
-
-// One render pass of the wave's ray over the n depths zs (LDS): k_render_jac_fold's forward and, JAC, its Jacobian
-// path.  Lane l owns the samples l B .. l B + B - 1, B = ceil(n / 64) <= MAXB.  w_out (LDS, n floats) or NULL;
-// jac (JAC): d depth / d (o, d), every lane the same six sums.
-template <int MAXB, bool JAC>
-__device__ __forceinline__ void pn_pass(const float (&row)[6], const float* zs, int n, const double* __restrict__ a,
-                                        float eps, int lane, float* w_out, double& dep, double& hit,
-                                        double (&jac)[6]) {
-  const int B = (n + 63) / 64;
-  const int i0 = lane * B;
-  const int nb = max(0, min(min(B, MAXB), n - i0));
-  // samples past the lane's block count as p = 0 at z = 0: factors of one and terms of zero everywhere below
-  float pv[MAXB], zv[MAXB];
-  double gx[JAC ? MAXB : 1][3];
-#pragma unroll
-  for (int j = 0; j < MAXB; ++j) {
-    pv[j] = 0.0f;
-    zv[j] = 0.0f;
-    if constexpr (JAC) gx[j][0] = gx[j][1] = gx[j][2] = 0.0;
-  }
-#pragma nounroll
-  for (int j = 0; j < nb; ++j) {   // a rolled loop (one copy of the 30 sincosf); the selects keep the indices static
-    const float z = zs[i0 + j];
-    float x[3];
-    sample_point(row, z, x);
-    double d[3];
-    const float ps = sigmoid_ref((float)pn_logit<JAC>(x, a, d));
-#pragma unroll
-    for (int jj = 0; jj < MAXB; ++jj) {
-      if (jj == j) {
-        pv[jj] = ps;
-        zv[jj] = z;
-        if constexpr (JAC) {
-          gx[jj][0] = d[0];
-          gx[jj][1] = d[1];
-          gx[jj][2] = d[2];
-        }
-      }
-    }
-  }
-  double loc = 1.0;
-#pragma unroll
-  for (int j = 0; j < MAXB; ++j) loc *= 1.0 - (double)pv[j];
-  double T = pn_excl_prod(loc, lane);
-  double wv[MAXB], tv[JAC ? MAXB : 1];
-  double sw = 0.0;
-#pragma unroll
-  for (int j = 0; j < MAXB; ++j) {
-    if constexpr (JAC) tv[j] = T;
-    wv[j] = T * (double)pv[j];
-    sw += wv[j];
-    T *= 1.0 - (double)pv[j];
-  }
-  hit = wave_sum_d(sw);
-  const double rden = 1.0 / (hit + (double)eps);
-  double sd = 0.0;
-#pragma unroll
-  for (int j = 0; j < MAXB; ++j) {
-    wv[j] = wv[j] * rden;
-    sd += wv[j] * (double)zv[j];
-  }
-  dep = wave_sum_d(sd);
-  if (w_out) {
-#pragma unroll
-    for (int j = 0; j < MAXB; ++j)
-      if (j < nb) w_out[i0 + j] = (float)wv[j];
-  }
-  if constexpr (JAC) {
-    // d depth / d logit_s (k_composite_bwd's recurrence with dL/ddepth = 1); wv is dead, its registers hold g
-#pragma unroll
-    for (int j = 0; j < MAXB; ++j) wv[j] = ((double)zv[j] - dep) * rden;   // d depth / d w~_j
-    double A = 0.0, Bm = 1.0;   // this lane's affine map U_end -> U_{i0 - 1}
-#pragma unroll
-    for (int j = MAXB - 1; j >= 0; --j) {
-      const double aj = wv[j] * (double)pv[j], bj = 1.0 - (double)pv[j];
-      A = aj + bj * A;
-      Bm = bj * Bm;
-    }
-    double U = pn_suffix_affine(A, Bm, lane);
-#pragma unroll
-    for (int j = MAXB - 1; j >= 0; --j) {
-      const double gp = tv[j] * (wv[j] - U);
-      U = wv[j] * (double)pv[j] + (1.0 - (double)pv[j]) * U;
-      wv[j] = gp * (1.0 - (double)pv[j]) * (double)pv[j];   // sigmoid backward: now d depth / d logit_j
-    }
-#pragma unroll
-    for (int m = 0; m < 6; ++m) jac[m] = 0.0;
-#pragma unroll
-    for (int j = 0; j < MAXB; ++j) {   // sample order
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const double g = wv[j] * gx[j][m];
-        jac[m] += g;
-        jac[3 + m] += (double)zv[j] * g;
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < 6; ++m) jac[m] = wave_sum_d(jac[m]);
-  }
-}
-
-// value a of cat(zc, fs)
-__device__ __forceinline__ float pn_cat(const float* zc, const float* fs, int S, int a) {
-  return a < S ? zc[a] : fs[a - S];
-}
-
-// k_resample at u == NULL and the merge with zc, on the wave's slice (localize.hip, step 4)
-__device__ __forceinline__ void pn_resample_merge(const float* zc, float* fs, const float* ws, float* cdf, float* zf,
-                                                  int S, int I, int lane) {
-  const int nbin = S - 1, npdf = nbin - 1;
-  const float* w = ws + 1;
-  const int B = (npdf + 63) / 64, i0 = lane * B;
-  double ls = 0.0;
-#pragma nounroll
-  for (int j = 0; j < B; ++j) {
-    const int i = i0 + j;
-    if (i < npdf) ls += (double)(w[i] + 1e-5f);
-  }
-  const float tot = (float)wave_sum_d(ls);
-  double lp = 0.0;
-#pragma nounroll
-  for (int j = 0; j < B; ++j) {
-    const int i = i0 + j;
-    if (i < npdf) lp += (double)((w[i] + 1e-5f) / tot);
-  }
-  double run = pn_excl_sum(lp, lane);
-  if (lane == 0) cdf[0] = 0.0f;
-#pragma nounroll
-  for (int j = 0; j < B; ++j) {
-    const int i = i0 + j;
-    if (i < npdf) {
-      run += (double)((w[i] + 1e-5f) / tot);
-      cdf[i + 1] = (float)run;
-    }
-  }
-  pn_wave_lds_sync();
-#pragma nounroll
-  for (int k = lane; k < I; k += 64) {
-    const float u = linspace01(k, I);
-    int lo = 0, hi = nbin;   // first index with cdf > u (searchsorted right=True)
-#pragma nounroll
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cdf[mid] <= u) lo = mid + 1; else hi = mid;
-    }
-    const int below = max(lo - 1, 0), above = max(min(lo, nbin - 1), 0);
-    const float c0 = cdf[below], c1 = cdf[above];
-    float denom = c1 - c0;
-    if (denom < 1e-5f) denom = 1.0f;
-    const float t = (u - c0) / denom;
-    const float b0 = 0.5f * (zc[below + 1] + zc[below]), b1 = 0.5f * (zc[above + 1] + zc[above]);
-    fs[k] = b0 + t * (b1 - b0);
-  }
-  pn_wave_lds_sync();   // (also orders the last ws / cdf read before zf's first write)
-  bool ok = true;
-#pragma nounroll
-  for (int i = lane; i < S; i += 64) ok = ok && (zc[i] == zc[i]) && (i + 1 >= S || zc[i] <= zc[i + 1]);
-#pragma nounroll
-  for (int k = lane; k < I; k += 64) ok = ok && (fs[k] == fs[k]) && (k + 1 >= I || fs[k] <= fs[k + 1]);
-  const int n = S + I;
-  if (__all(ok)) {
-#pragma nounroll
-    for (int i = lane; i < S; i += 64) {
-      const float v = zc[i];
-      int lo = 0, hi = I;
-#pragma nounroll
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (fs[mid] < v) lo = mid + 1; else hi = mid;
-      }
-      zf[min(i + lo, n - 1)] = v;
-    }
-#pragma nounroll
-    for (int k = lane; k < I; k += 64) {
-      const float v = fs[k];
-      int lo = 0, hi = S;
-#pragma nounroll
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (zc[mid] <= v) lo = mid + 1; else hi = mid;
-      }
-      zf[min(k + lo, n - 1)] = v;
-    }
-  } else {
-#pragma nounroll
-    for (int a = lane; a < n; a += 64) {
-      const float va = pn_cat(zc, fs, S, a);
-      const bool na = !(va == va);
-      int rank = 0;
-#pragma nounroll
-      for (int b = 0; b < n; ++b) {
-        const float vb = pn_cat(zc, fs, S, b);
-        const bool nb = !(vb == vb);
-        rank += (vb < va) || (na && !nb) || ((vb == va || (na && nb)) && b < a);   // NaNs after every number
-      }
-      zf[min(rank, n - 1)] = va;
-    }
-  }
-  pn_wave_lds_sync();
-}
 
 template <int MAXB>
 __global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
@@ -347,77 +57,35 @@ __global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
   const int64_t beam = (int64_t)(blockIdx.x - (unsigned)pose * (unsigned)bpp) * 4 + wave;
   double mine = 0.0;   // lane k < 29: term k of this wave's beam
   if (beam < n_beams) {   // (wave-uniform: the shuffles below always have 64 lanes)
-    float* zc = pn_lds + (size_t)wave * pn_slice_floats(S, I);
+    float* zc = pn_lds + (size_t)wave * fr_slice_floats(S, I);
     float* fs = zc + S;
     float* ws = fs + I;      // coarse weights (S)
     float* cdf = ws + S;     // (S - 1)
     float* zf = ws;          // the merged depths (S + I): ws and cdf are dead when it is written
     // 1. the ray (every lane the same values)
-    const double* T = pb;
-    const double* box = pb + 12;
-    const float* __restrict__ pt = points + 3 * beam;
-    const double px = (double)pt[0], py = (double)pt[1], pz = (double)pt[2];
-    const double rng = sqrt((px * px + py * py) + pz * pz);
-    const double ux = px / rng, uy = py / rng, uz = pz / rng;
-    double d[3], o[3];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      d[m] = (T[3 * m] * ux + T[3 * m + 1] * uy) + T[3 * m + 2] * uz;
-      o[m] = T[9 + m];
-    }
-    const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    const double nan64 = __builtin_nan("");
-    double tmin = 0.0;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      d[m] = d[m] / dn;
-      const double inv = 1.0 / d[m];
-      const double t1 = (box[m] - o[m]) * inv, t2 = (box[3 + m] - o[m]) * inv;
-      // torch.maximum / min propagate NaN; a NaN t2 counts as +inf
-      const double tm = t2 != t2 ? (double)INFINITY : (t1 != t1 ? nan64 : fmax(t1, t2));
-      tmin = m == 0 ? tm : ((tmin != tmin || tm != tm) ? nan64 : fmin(tmin, tm));
-    }
-    const double far64 = tmin != tmin ? tmin : fmax(tmin, (double)near);
-    float row[6];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      row[m] = (float)o[m];
-      row[3 + m] = (float)d[m];
-    }
-    const float far = (float)far64, target = (float)rng;
+    float row[6], far, target;
+    fr_pose_ray(pb, points + 3 * beam, near, row, far, target);
     // 2. coarse depths
 #pragma nounroll
     for (int i = lane; i < S; i += 64) zc[i] = lerp_z(near, far, linspace01(i, S));
-    pn_wave_lds_sync();
+    wave_lds_sync();
     // 3. the coarse pass (no Jacobian), 4. resampling and the merge, 5. the fine pass with its Jacobian
     double dep = 0.0, hit = 0.0, jac[6];
-    pn_pass<MAXB, false>(row, zc, S, fa[0], eps, lane, ws, dep, hit, jac);
-    pn_wave_lds_sync();
-    pn_resample_merge(zc, fs, ws, cdf, zf, S, I, lane);
-    pn_pass<MAXB, true>(row, zf, S + I, fa[1], eps, lane, nullptr, dep, hit, jac);
+    fr_pass<MAXB, false>(row, zc, S, fa[0], eps, lane, ws, dep, hit, jac);
+    wave_lds_sync();
+    fr_resample_merge(zc, fs, ws, cdf, zf, S, I, lane);
+    fr_pass<MAXB, true>(row, zf, S + I, fa[1], eps, lane, nullptr, dep, hit, jac);
     // 6. k_gn_normal_eq's terms, on the float32 values the composed route hands to it
     const float dv = (float)dep, sv = (float)hit;
     float jf[6];
 #pragma unroll
     for (int m = 0; m < 6; ++m) jf[m] = (float)jac[m];
     const double delta = pb[18], min_sumw = pb[19];
-    const bool valid = (double)sv >= min_sumw && isfinite(dv) && isfinite(target) && target > 0.0f;
-    if (valid) {
-      double ro[3], rd[3], Jo[3], Jd[3], Jp[6];
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        ro[m] = (double)row[m];
-        rd[m] = (double)row[3 + m];
-        Jo[m] = (double)jf[m];
-        Jd[m] = (double)jf[3 + m];
-        Jp[m] = Jo[m];
-      }
-      Jp[3] = (ro[1] * Jo[2] - ro[2] * Jo[1]) + (rd[1] * Jd[2] - rd[2] * Jd[1]);
-      Jp[4] = (ro[2] * Jo[0] - ro[0] * Jo[2]) + (rd[2] * Jd[0] - rd[0] * Jd[2]);
-      Jp[5] = (ro[0] * Jo[1] - ro[1] * Jo[0]) + (rd[0] * Jd[1] - rd[1] * Jd[0]);
-      const double res = (double)dv - (double)target, ar = fabs(res);
-      const bool lin = delta > 0.0 && ar > delta;   // Huber's linear branch; delta <= 0: plain least squares
-      const double w = lin ? delta / ar : 1.0;
+    if (gn_beam_valid(dv, sv, target, min_sumw)) {
+      double Jp[6], w, rho;
+      gn_pose_jacobian(row, jf, Jp);
+      const double res = (double)dv - (double)target;
+      gn_huber(res, delta, w, rho);
       int k = 0;
 #pragma unroll
       for (int p = 0; p < 6; ++p) {
@@ -429,7 +97,7 @@ __global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
         }
         if (lane == 21 + p) mine = wj * res;
       }
-      if (lane == 27) mine = lin ? delta * (ar - 0.5 * delta) : 0.5 * (res * res);
+      if (lane == 27) mine = rho;
       if (lane == 28) mine = 1.0;
     }
     if (lane == 0) {
@@ -683,20 +351,11 @@ __global__ __launch_bounds__(64) void k_se3_apply(const double* __restrict__ xi6
   for (int k = 0; k < 12; ++k) poses12_out[12 * p + k] = out[k];
 }
 
-inline int64_t pn_blocks_per_pose(int64_t n_beams) { return (n_beams + 3) / 4; }
 inline unsigned lm_blocks(int64_t n) { return (unsigned)((n + 63) / 64); }
-
-void pn_check_samples(const char* name, int n_samples, int n_importance) {
-  const std::string who(name);
-  PCN_CHECK(n_samples >= 3, who + ": n_samples < 3 (the resampling needs one interior weight)");
-  PCN_CHECK(n_importance >= 1, who + ": n_importance < 1");
-  PCN_CHECK((int64_t)n_samples + n_importance <= PN_MAX_S,
-            who + ": n_samples + n_importance > 1024 (one wave per beam, at most 16 samples per lane)");
-}
 
 size_t pn_workspace_bytes(int64_t n_poses, int64_t n_beams) {
   if (n_poses <= 0 || n_beams <= 0) return 0;
-  return (size_t)n_poses * (size_t)pn_blocks_per_pose(n_beams) * PN_W * sizeof(double);
+  return (size_t)n_poses * (size_t)fr_blocks_per_pose(n_beams) * PN_W * sizeof(double);
 }
 
 // every check an evaluation makes, before anything is launched (n_poses > 0)
@@ -707,9 +366,7 @@ void pn_check_eval(const char* name, const float* points, int64_t n_beams, int64
   PCN_CHECK(points && box6 && fold_c && fold_f && workspace, who + ": null argument");
   PCN_CHECK(workspace_bytes >= pn_workspace_bytes(n_poses, n_beams),
             who + ": workspace smaller than pcnerf_pose_normal_eq_workspace_bytes");
-  const int64_t bpp = pn_blocks_per_pose(n_beams);
-  PCN_CHECK(bpp < (int64_t)1 << 31 && n_poses < (int64_t)1 << 31 && n_poses * bpp < (int64_t)1 << 31,
-            who + ": too many (pose, beam) pairs for one launch");
+  fr_check_pairs(name, n_poses, n_beams);
 }
 
 // one evaluation of all running poses (checked by pn_check_eval); n_poses > 0
@@ -721,20 +378,14 @@ void pn_launch_eval(const float* points, int64_t n_beams, const double* poses12,
     PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), stream));
     return;
   }
-  const int64_t bpp = pn_blocks_per_pose(n_beams);
-  const size_t lds = (size_t)4 * pn_slice_floats(S, I) * sizeof(float);   // <= 48 KiB
-  const int B = (S + I + 63) / 64;
+  const int64_t bpp = fr_blocks_per_pose(n_beams);
+  const size_t lds = (size_t)4 * fr_slice_floats(S, I) * sizeof(float);   // <= 48 KiB
   double* part = reinterpret_cast<double*>(workspace);
-#define PN_LAUNCH(MB)                                                                                          \
-  hipLaunchKernelGGL(k_pose_normal_eq_fold<MB>, dim3((unsigned)(n_poses * bpp)), dim3(256), lds, stream, points, \
-                     n_beams, poses12, state, (int)bpp, box6, near, S, I, fold_c, fold_f, eps, delta, min_sumw, \
-                     part, depth, sumw, jac6)
-  if (B <= 1) PN_LAUNCH(1);
-  else if (B <= 2) PN_LAUNCH(2);
-  else if (B <= 4) PN_LAUNCH(4);
-  else if (B <= 8) PN_LAUNCH(8);
-  else PN_LAUNCH(16);
-#undef PN_LAUNCH
+  fr_dispatch_maxb(S + I, [&](auto mb) {
+    hipLaunchKernelGGL(k_pose_normal_eq_fold<decltype(mb)::value>, dim3((unsigned)(n_poses * bpp)), dim3(256), lds,
+                       stream, points, n_beams, poses12, state, (int)bpp, box6, near, S, I, fold_c, fold_f, eps, delta,
+                       min_sumw, part, depth, sumw, jac6);
+  });
   hipLaunchKernelGGL(k_pose_normal_eq_sum, dim3((unsigned)n_poses), dim3(256), 0, stream, part, (int)bpp, state,
                      normal30);
 }
@@ -742,15 +393,6 @@ void pn_launch_eval(const float* points, int64_t n_beams, const double* poses12,
 }  // namespace pcn
 
 using namespace pcn;
-
-// these entries report an argument error as -1 (the message in pcnerf_last_error)
-#define REF_API_END                                       \
-  return 0;                                               \
-  }                                                       \
-  catch (const std::exception& ex__) {                    \
-    pcn::set_error(ex__.what());                          \
-    return -1;                                            \
-  }
 
 extern "C" size_t pcnerf_pose_normal_eq_workspace_bytes(int64_t n_poses, int64_t n_beams) {
   return pn_workspace_bytes(n_poses, n_beams);
@@ -766,7 +408,7 @@ extern "C" int pcnerf_pose_normal_eq_fold(const float* points_sensor, int64_t n_
   PCN_API_BEGIN
   const char* who = "pcnerf_pose_normal_eq_fold";
   PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_pose_normal_eq_fold: negative count");
-  pn_check_samples(who, n_samples, n_importance);
+  fr_check_samples(who, n_samples, n_importance);
   if (n_poses == 0) return 0;
   PCN_CHECK(normal30 && (poses12_or_null || state_or_null), "pcnerf_pose_normal_eq_fold: null argument");
   pn_check_eval(who, points_sensor, n_beams, n_poses, parent_box6, fold_coarse, fold_fine, workspace,
@@ -775,7 +417,7 @@ extern "C" int pcnerf_pose_normal_eq_fold(const float* points_sensor, int64_t n_
                  n_importance, fold_coarse, fold_fine, eps, huber_delta, min_sumw, workspace, normal30, depth_or_null,
                  sumw_or_null, jac6_or_null, (hipStream_t)stream);
   PCN_LAUNCH_CHECK(who);
-  REF_API_END
+  PCN_API_END_NEG
 }
 
 extern "C" int pcnerf_lm_init(const double* poses12, int64_t n_poses, double damping, double* state, void* stream) {
@@ -787,7 +429,7 @@ extern "C" int pcnerf_lm_init(const double* poses12, int64_t n_poses, double dam
   hipLaunchKernelGGL(k_lm_init, dim3(lm_blocks(n_poses * LM_STATE)), dim3(64), 0, (hipStream_t)stream, poses12,
                      n_poses, damping, state);
   PCN_LAUNCH_CHECK("pcnerf_lm_init");
-  REF_API_END
+  PCN_API_END_NEG
 }
 
 extern "C" int pcnerf_lm_update(const double* normal30, int64_t n_poses, double xi_tol, double* state,
@@ -803,7 +445,7 @@ extern "C" int pcnerf_lm_update(const double* normal30, int64_t n_poses, double 
   hipLaunchKernelGGL(k_lm_update, dim3(lm_blocks(n_poses)), dim3(64), 0, (hipStream_t)stream, normal30, n_poses,
                      xi_tol, state, eval_costs_or_null, accepted_or_null, iter_index, iters);
   PCN_LAUNCH_CHECK("pcnerf_lm_update");
-  REF_API_END
+  PCN_API_END_NEG
 }
 
 extern "C" int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_beams, const double* poses12,
@@ -817,7 +459,7 @@ extern "C" int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_be
   const char* who = "pcnerf_refine_poses_fold";
   PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_refine_poses_fold: negative count");
   PCN_CHECK(iters >= 0, "pcnerf_refine_poses_fold: iters < 0");
-  pn_check_samples(who, n_samples, n_importance);
+  fr_check_samples(who, n_samples, n_importance);
   if (n_poses == 0) return 0;
   PCN_CHECK(poses12 && normal30 && state && poses12_out, "pcnerf_refine_poses_fold: null argument");
   PCN_CHECK(iters == 0 || (eval_costs && accepted), "pcnerf_refine_poses_fold: null argument");
@@ -841,7 +483,7 @@ extern "C" int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_be
   }
   hipLaunchKernelGGL(k_lm_poses_out, dim3(lm_blocks(n_poses * 12)), dim3(64), 0, s, state, n_poses, poses12_out);
   PCN_LAUNCH_CHECK(who);
-  REF_API_END
+  PCN_API_END_NEG
 }
 
 extern "C" int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, double* poses12_out,
@@ -854,5 +496,5 @@ extern "C" int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_
   hipLaunchKernelGGL(k_se3_apply, dim3(lm_blocks(n_poses)), dim3(64), 0, (hipStream_t)stream, xi6, poses12, n_poses,
                      poses12_out);
   PCN_LAUNCH_CHECK("pcnerf_se3_apply");
-  REF_API_END
+  PCN_API_END_NEG
 }

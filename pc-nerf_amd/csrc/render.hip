@@ -127,28 +127,7 @@ __global__ void k_perturb(const float* __restrict__ z, int64_t total, int S, flo
 }
 
 // ------------------------------------------------------------------------------- compositing
-// Exclusive multiplicative scan of one double per lane across the wave.
-__device__ __forceinline__ double wave_excl_prod(double v, int lane) {
-  double incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(incl, o, 64);
-    if (lane >= o) incl *= n;
-  }
-  const double ex = __shfl_up(incl, 1, 64);
-  return lane == 0 ? 1.0 : ex;
-}
-__device__ __forceinline__ double wave_excl_sum(double v, int lane) {
-  double incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += n;
-  }
-  const double ex = __shfl_up(incl, 1, 64);
-  return lane == 0 ? 0.0 : ex;
-}
-
+// (the wave scans wave_excl_prod and wave_excl_sum: common.h)
 // A ray's compositing group: one wave (G = 64, four rays per 256-thread workgroup: the many-ray batches) or one
 // whole workgroup (G = 256: batches of a few hundred long rays, e.g. the reference shell's 256 rays x 2,304 fine
 // samples, where a wave per ray kept 64 of 256 CUs busy and 36 samples per lane spilled).  Thread t of the group
@@ -421,9 +400,7 @@ __global__ __launch_bounds__(256) void k_depth2_ties(const float* __restrict__ W
     if (j < S - 1) tie = tie || !(kv_desc(x, wl) || kv_desc(wl, x));
   }
   if (__ballot(tie) == 0) return;   // (wave-uniform)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   if (lane == 0) {
     introsort_desc(V, I, S);
     int pos = 0;

@@ -10,17 +10,6 @@
 
 namespace pcn {
 
-__device__ __forceinline__ double view_excl_prod(double v, int lane) {
-  double incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double n = __shfl_up(incl, o, 64);
-    if (lane >= o) incl *= n;
-  }
-  const double ex = __shfl_up(incl, 1, 64);
-  return lane == 0 ? 1.0 : ex;
-}
-
 // scipy 'reflect' extension (d c b a | a b c d | d c b a), any distance
 __device__ __forceinline__ int reflect_index(int j, int n) {
   const int p = 2 * n;
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(256) void k_view_rows(const float* __restrict__ P, 
     const float pj = pr[j];
     op += (double)((pcn::log32(0.1f + pj) + pcn::log32(0.1f + (1.0f - pj))) + 2.20727f);
   }
-  double T = view_excl_prod(loc, lane);
+  double T = wave_excl_prod(loc, lane);
   double sw = 0.0;
 #pragma unroll
   for (int j = 0; j < MAXB; ++j) {
@@ -127,9 +116,7 @@ __global__ __launch_bounds__(256) void k_view_rows(const float* __restrict__ P, 
   const float d = (float)wave_sum_d(sd);
   // Gaussian smoothing of the weight row (scipy correlate1d, symmetric kernel: x[k]*w0 + sum over the outer
   // taps first of (x[k-j] + x[k+j]) * w_j, in float64, rounded to float32) and its first argmax
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   float best = -__builtin_inff();
   int bidx = 0x7fffffff;
   for (int j = 0; j < nb; ++j) {
