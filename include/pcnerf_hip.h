@@ -661,6 +661,81 @@ int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_beams, const 
                              double* eval_costs, uint8_t* accepted, void* stream);
 int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, double* poses12_out, void* stream);
 
+/* ---------------------------------------------------------------- localisation against a map of blocks
+ * The scoring and the refinement above with every pose rendered against its own parent block, in one launch for
+ * the whole set (no reference counterpart: a PC-NeRF map is several blocks, each with its own pair of networks and
+ * its own AABB).  A map is n_blocks >= 1 blocks: folds_coarse / folds_fine (n_blocks, 64) float64, row b =
+ * pcnerf_nof_fold_eval's output of block b; boxes6 (n_blocks, 6) float64 rows [lo (3), hi (3)], which may overlap.
+ * block_of_pose (n_poses) int32: the block of each pose; -1, and any index outside 0 .. n_blocks - 1, renders
+ * nothing and is never used as an index.  For a pose with block b every output equals, bit for bit, what the
+ * single-block entry gives for that pose with block b's folds and box.  A beam is clipped at the exit from its
+ * block's box; nothing is composited across blocks.  Argument errors return -1 before anything is launched.
+ *
+ * pcnerf_assign_blocks: block_of_pose[p] = the block whose box contains t_p (lo + margin <= t <= hi - margin on all
+ *   three axes, float64) with the largest clearance min_m min(t_m - lo_m, hi_m - t_m), the lowest index on equal
+ *   clearance; -1 when none contains it or a component of t_p is NaN.
+ * pcnerf_score_poses_map: pcnerf_score_poses_fold's operands and outputs; the scores4 row of a pose without a block
+ *   is zero, its depth NaN and its sumw 0.  `workspace` needs pcnerf_score_poses_workspace_bytes.
+ * pcnerf_pose_normal_eq_map: pcnerf_pose_normal_eq_fold's operands and outputs; the normal30 row of a pose without a
+ *   block (as of a stopped pose) is zero and its per-beam rows are not written.  `workspace` needs
+ *   pcnerf_pose_normal_eq_workspace_bytes.
+ * pcnerf_refine_poses_map: pcnerf_refine_poses_fold with pcnerf_pose_normal_eq_map as the evaluation; the block of a
+ *   pose is fixed for the call.  A pose without a block stops with status 2 at the first update (zero valid beams)
+ *   and poses12_out returns its input bits. */
+int pcnerf_assign_blocks(const double* poses12, int64_t n_poses, const double* boxes6, int n_blocks, double margin,
+                         int32_t* block_of_pose, void* stream);
+int pcnerf_score_poses_map(const float* points_sensor, int64_t n_beams, const double* poses12, int64_t n_poses,
+                           const int32_t* block_of_pose, int n_blocks, const double* boxes6, float near,
+                           int n_samples, int n_importance, const double* folds_coarse, const double* folds_fine,
+                           float eps, double huber_delta, double min_sumw, void* workspace, size_t workspace_bytes,
+                           double* scores4, float* depth_or_null, float* sumw_or_null, void* stream);
+int pcnerf_pose_normal_eq_map(const float* points_sensor, int64_t n_beams, const double* poses12_or_null,
+                              int64_t n_poses, const double* state_or_null, const int32_t* block_of_pose,
+                              int n_blocks, const double* boxes6, float near, int n_samples, int n_importance,
+                              const double* folds_coarse, const double* folds_fine, float eps, double huber_delta,
+                              double min_sumw, void* workspace, size_t workspace_bytes, double* normal30,
+                              float* depth_or_null, float* sumw_or_null, float* jac6_or_null, void* stream);
+int pcnerf_refine_poses_map(const float* points_sensor, int64_t n_beams, const double* poses12, int64_t n_poses,
+                            const int32_t* block_of_pose, int n_blocks, const double* boxes6, float near,
+                            int n_samples, int n_importance, const double* folds_coarse, const double* folds_fine,
+                            float eps, double huber_delta, double min_sumw, double damping, double xi_tol, int iters,
+                            void* workspace, size_t workspace_bytes, double* normal30, double* state,
+                            double* poses12_out, double* eval_costs, uint8_t* accepted, void* stream);
+
+/* ---------------------------------------------------------------- particle-filter update (Monte-Carlo localisation)
+ * Weights, effective sample size and systematic resampling of a particle set on the device, in float64, with no
+ * host synchronisation: every scalar that steers a later launch (n_usable, u0, ess) is read from device memory.  No
+ * atomics; launch geometry and summation order depend on n_particles alone.  Argument errors return -1.
+ *
+ * pcnerf_mcl_weights: scores4 (n, 4) = pcnerf_score_poses_map's rows, n_usable_dev one float64 on the device (the
+ *   scan's beams with a finite range > 0).  mean_p = (cost_p + miss_cost (n_usable - n_valid_p)) / n_usable,
+ *   logw_p = logw_prev_p - beta mean_p, -inf where block_of_pose[p] < 0, mean_p is not finite or the result is NaN
+ *   or +inf.  With m = max logw and Z = sum exp(logw - m): w_p = exp(logw_p - m) / Z, logw_p <- logw_p - m - log Z,
+ *   ess[0] = Z^2 / sum exp(logw - m)^2 (= 1 / sum w^2), best[0] = the lowest index attaining m, degenerate[0] = 0.
+ *   No finite logw: w = 1 / n, logw = 0, ess = n, best = 0, degenerate = 1.  1 <= n <= 4,194,304.
+ *   Precondition: block_of_pose holds -1 .. n_blocks - 1 (what pcnerf_assign_blocks writes).  The entry does not know
+ *   n_blocks: an id >= n_blocks, which the render entries treat as "no block" (a zero scores4 row), is NOT given
+ *   -inf here but the finite weight of a pose that missed every beam; map such ids to -1 first.
+ * pcnerf_systematic_resample: c = the inclusive prefix sums of w (negative, NaN and infinite weights count as 0) by
+ *   a fixed-order hierarchical scan in which a zero weight gives c_i == c_{i-1} exactly; C = c_{n-1};
+ *   u_j = (j + u0) / n_out * C with u0_dev[0] in [0, 1) (anything else counts as 0);
+ *   ancestors[j] = the first i with c_i > u_j, clamped to the last i with w_i > 0.  With ess_dev_or_null given (the
+ *   ESS switch; n_out must equal n) and ess[0] >= ess_threshold nothing is resampled: ancestors = 0 .. n - 1 and
+ *   logw_out = logw; otherwise logw_out = 0.  poses12_out (n_out, 12), blocks_out (n_out) and logw_out (n_out), each
+ *   optional with its input, are gathered by the ancestors.  1 <= n <= 4,194,304 (one thread walks the
+ *   ceil(n / 1024) block totals as a serial chain). */
+size_t pcnerf_mcl_weights_workspace_bytes(int64_t n_particles);
+int pcnerf_mcl_weights(const double* logw_prev, const double* scores4, const int32_t* block_of_pose,
+                       int64_t n_particles, const double* n_usable_dev, double miss_cost, double beta,
+                       void* workspace, size_t workspace_bytes, double* w, double* logw, double* ess, int32_t* best,
+                       int32_t* degenerate, void* stream);
+size_t pcnerf_systematic_resample_workspace_bytes(int64_t n_particles);
+int pcnerf_systematic_resample(const double* w, int64_t n_particles, const double* u0_dev, int64_t n_out,
+                               const double* ess_dev_or_null, double ess_threshold, const double* poses12_or_null,
+                               const int32_t* blocks_or_null, const double* logw_or_null, void* workspace,
+                               size_t workspace_bytes, int32_t* ancestors, double* poses12_out_or_null,
+                               int32_t* blocks_out_or_null, double* logw_out_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -830,3 +830,285 @@ def se3_apply(xi6: Tensor, poses12: Tensor) -> Tensor:
 @se3_apply.register_fake
 def _(xi6, poses12):
     return poses12.new_empty(tuple(poses12.shape), dtype=torch.float64)
+
+
+# ----------------------------------------------------------------------------------------------- maps of blocks
+# score_poses_fold / pose_normal_eq_fold / refine_poses_fold with every pose rendered against its own block
+# (nof.localization.BlockMap: folds (B, 64), boxes (B, 6)), and the particle-filter update of nof.mcl.  Read no
+# process-wide selector.
+def _need_on_device(op: str, *ts: Optional[Tensor]) -> None:
+    """Every operand is a ROCm device tensor on one device (int32 block ids included)."""
+    dev = None
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"pcnerf::{op}: pcnerf_hip kernels take ROCm device tensors (got {t.dtype} on "
+                               f"{t.device}); this package has no CPU path")
+        if dev is not None and t.device != dev:
+            raise RuntimeError(f"pcnerf::{op}: operands are on different devices")
+        dev = t.device
+
+
+def _check_map(op: str, boxes6: Tensor, folds_coarse: Tensor, folds_fine: Tensor) -> int:
+    _layout(op, "boxes6", boxes6, (("min", 1), 6), torch.float64)
+    B = boxes6.shape[0]
+    _layout(op, "folds_coarse", folds_coarse, (B, 64), torch.float64)
+    _layout(op, "folds_fine", folds_fine, (B, 64), torch.float64)
+    return B
+
+
+@torch.library.custom_op(f"{NS}::assign_blocks", mutates_args=())
+def assign_blocks(poses12: Tensor, boxes6: Tensor, margin: float) -> Tensor:
+    """(P,) int32: per poses12 (P, 12) row the block of boxes6 (B, 6) = [lo, hi] rows that contains the translation
+    with ``margin`` to spare on every side and has the largest clearance (lowest index on ties); -1 for none or a NaN
+    translation (pcnerf_assign_blocks)."""
+    op = "assign_blocks"
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "boxes6", boxes6, (("min", 1), 6), torch.float64)
+    _need_on_device(op, poses12, boxes6)
+    out = torch.empty((poses12.shape[0],), dtype=torch.int32, device=poses12.device)
+    H.check(H.lib().pcnerf_assign_blocks(poses12.data_ptr(), poses12.shape[0], boxes6.data_ptr(), boxes6.shape[0],
+                                         float(margin), out.data_ptr(), H.stream_of(poses12)))
+    return out
+
+
+@assign_blocks.register_fake
+def _(poses12, boxes6, margin):
+    return poses12.new_empty((poses12.shape[0],), dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{NS}::score_poses_map", mutates_args=())
+def score_poses_map(points: Tensor, poses12: Tensor, block_of_pose: Tensor, boxes6: Tensor, folds_coarse: Tensor,
+                    folds_fine: Tensor, near: float, n_samples: int, n_importance: int, eps: float,
+                    huber_delta: float, min_sumw: float, want_depth: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """score_poses_fold with pose p rendered against block block_of_pose[p] (int32 (P,)) of the map boxes6 (B, 6),
+    folds_coarse / folds_fine (B, 64): the same bits per pose as score_poses_fold with that block alone.  A pose with
+    -1 (or any index outside 0 .. B - 1) gets a zero scores4 row, NaN depth and zero sumw (pcnerf_score_poses_map)."""
+    op = "score_poses_map"
+    _layout(op, "points", points, (None, 3))
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "block_of_pose", block_of_pose, (poses12.shape[0],), torch.int32)
+    B = _check_map(op, boxes6, folds_coarse, folds_fine)
+    check_score_samples(op, n_samples, n_importance)
+    _need_on_device(op, points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine)
+    R, Pn = points.shape[0], poses12.shape[0]
+    dev = points.device
+    scores = torch.empty((Pn, 4), dtype=torch.float64, device=dev)
+    depth = torch.empty((Pn, R) if want_depth else (0,), dtype=torch.float32, device=dev)
+    sumw = torch.empty((Pn, R) if want_depth else (0,), dtype=torch.float32, device=dev)
+    nbytes = int(H.lib().pcnerf_score_poses_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_score_poses_map(points.data_ptr(), R, poses12.data_ptr(), Pn, block_of_pose.data_ptr(), B,
+                                           boxes6.data_ptr(), float(near), int(n_samples), int(n_importance),
+                                           folds_coarse.data_ptr(), folds_fine.data_ptr(), float(eps),
+                                           float(huber_delta), float(min_sumw), ws.data_ptr(), nbytes,
+                                           scores.data_ptr(), depth.data_ptr() if want_depth else None,
+                                           sumw.data_ptr() if want_depth else None, H.stream_of(points)))
+    return scores, depth, sumw
+
+
+@score_poses_map.register_fake
+def _(points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine, near, n_samples, n_importance, eps,
+      huber_delta, min_sumw, want_depth):
+    R, Pn = points.shape[0], poses12.shape[0]
+    return (points.new_empty((Pn, 4), dtype=torch.float64),
+            points.new_empty((Pn, R) if want_depth else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R) if want_depth else (0,), dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{NS}::pose_normal_eq_map", mutates_args=())
+def pose_normal_eq_map(points: Tensor, poses12: Optional[Tensor], state: Optional[Tensor], block_of_pose: Tensor,
+                       boxes6: Tensor, folds_coarse: Tensor, folds_fine: Tensor, near: float, n_samples: int,
+                       n_importance: int, eps: float, huber_delta: float, min_sumw: float,
+                       want_beams: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """pose_normal_eq_fold with pose p rendered against block block_of_pose[p] of the map: the same bits per pose.
+    The rows of a pose without a block are zero, as a stopped pose's (pcnerf_pose_normal_eq_map)."""
+    op = "pose_normal_eq_map"
+    _layout(op, "points", points, (None, 3))
+    if state is None and poses12 is None:
+        raise RuntimeError(f"pcnerf::{op}: one of poses12 and state is needed")
+    if state is not None:
+        _layout(op, "state", state, (None, LM_STATE_DOUBLES), torch.float64)
+    else:
+        _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    src = state if state is not None else poses12
+    _layout(op, "block_of_pose", block_of_pose, (src.shape[0],), torch.int32)
+    B = _check_map(op, boxes6, folds_coarse, folds_fine)
+    check_score_samples(op, n_samples, n_importance)
+    _need_on_device(op, points, src, block_of_pose, boxes6, folds_coarse, folds_fine)
+    R, Pn = points.shape[0], src.shape[0]
+    dev = points.device
+    n30 = torch.zeros((Pn, 30), dtype=torch.float64, device=dev)
+    depth = torch.zeros((Pn, R) if want_beams else (0,), dtype=torch.float32, device=dev)
+    sumw = torch.zeros((Pn, R) if want_beams else (0,), dtype=torch.float32, device=dev)
+    jac = torch.zeros((Pn, R, 6) if want_beams else (0,), dtype=torch.float32, device=dev)
+    nbytes = int(H.lib().pcnerf_pose_normal_eq_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_pose_normal_eq_map(points.data_ptr(), R, None if state is not None else poses12.data_ptr(),
+                                              Pn, state.data_ptr() if state is not None else None,
+                                              block_of_pose.data_ptr(), B, boxes6.data_ptr(), float(near),
+                                              int(n_samples), int(n_importance), folds_coarse.data_ptr(),
+                                              folds_fine.data_ptr(), float(eps), float(huber_delta), float(min_sumw),
+                                              ws.data_ptr(), nbytes, n30.data_ptr(),
+                                              depth.data_ptr() if want_beams else None,
+                                              sumw.data_ptr() if want_beams else None,
+                                              jac.data_ptr() if want_beams else None, H.stream_of(points)))
+    return n30, depth, sumw, jac
+
+
+@pose_normal_eq_map.register_fake
+def _(points, poses12, state, block_of_pose, boxes6, folds_coarse, folds_fine, near, n_samples, n_importance, eps,
+      huber_delta, min_sumw, want_beams):
+    R, Pn = points.shape[0], (state if state is not None else poses12).shape[0]
+    return (points.new_empty((Pn, 30), dtype=torch.float64),
+            points.new_empty((Pn, R) if want_beams else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R) if want_beams else (0,), dtype=torch.float32),
+            points.new_empty((Pn, R, 6) if want_beams else (0,), dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{NS}::refine_poses_map", mutates_args=())
+def refine_poses_map(points: Tensor, poses12: Tensor, block_of_pose: Tensor, boxes6: Tensor, folds_coarse: Tensor,
+                     folds_fine: Tensor, near: float, n_samples: int, n_importance: int, eps: float,
+                     huber_delta: float, min_sumw: float, damping: float, xi_tol: float,
+                     iters: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """refine_poses_fold with pose p refined against block block_of_pose[p] of the map, fixed for the call: the same
+    bits per pose.  A pose without a block stops with status 2 at the first update and returns its input
+    (pcnerf_refine_poses_map)."""
+    op = "refine_poses_map"
+    _layout(op, "points", points, (None, 3))
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "block_of_pose", block_of_pose, (poses12.shape[0],), torch.int32)
+    B = _check_map(op, boxes6, folds_coarse, folds_fine)
+    check_score_samples(op, n_samples, n_importance)
+    if iters < 0:
+        raise RuntimeError(f"pcnerf::{op}: iters = {iters} is negative")
+    _need_on_device(op, points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine)
+    R, Pn = points.shape[0], poses12.shape[0]
+    dev = points.device
+    out = torch.zeros((Pn, 12), dtype=torch.float64, device=dev)
+    state = torch.zeros((Pn, LM_STATE_DOUBLES), dtype=torch.float64, device=dev)
+    costs = torch.full((Pn, iters), float("nan"), dtype=torch.float64, device=dev)
+    acc = torch.zeros((Pn, iters), dtype=torch.uint8, device=dev)
+    n30 = torch.empty((max(Pn, 1), 30), dtype=torch.float64, device=dev)
+    nbytes = int(H.lib().pcnerf_pose_normal_eq_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_refine_poses_map(points.data_ptr(), R, poses12.data_ptr(), Pn, block_of_pose.data_ptr(), B,
+                                            boxes6.data_ptr(), float(near), int(n_samples), int(n_importance),
+                                            folds_coarse.data_ptr(), folds_fine.data_ptr(), float(eps),
+                                            float(huber_delta), float(min_sumw), float(damping), float(xi_tol),
+                                            int(iters), ws.data_ptr(), nbytes, n30.data_ptr(), state.data_ptr(),
+                                            out.data_ptr(), costs.data_ptr(), acc.data_ptr(), H.stream_of(points)))
+    return out, state, costs, acc
+
+
+@refine_poses_map.register_fake
+def _(points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine, near, n_samples, n_importance, eps,
+      huber_delta, min_sumw, damping, xi_tol, iters):
+    Pn = poses12.shape[0]
+    return (points.new_empty((Pn, 12), dtype=torch.float64),
+            points.new_empty((Pn, LM_STATE_DOUBLES), dtype=torch.float64),
+            points.new_empty((Pn, iters), dtype=torch.float64), points.new_empty((Pn, iters), dtype=torch.uint8))
+
+
+MCL_MAX_PARTICLES = 1 << 22   # pcnerf_mcl_weights / pcnerf_systematic_resample (re-reduced partials, serial chains)
+
+
+@torch.library.custom_op(f"{NS}::mcl_weights", mutates_args=())
+def mcl_weights(logw_prev: Tensor, scores4: Tensor, block_of_pose: Tensor, n_usable: Tensor, miss_cost: float,
+                beta: float) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(w (P,), logw (P,), ess (1,) float64, best (1,), degenerate (1,) int32) of the particle weights
+    logw = logw_prev - beta (cost + miss_cost (n_usable - n_valid)) / n_usable from the scores4 (P, 4) rows, -inf
+    without a block or with a non-finite mean, normalised in float64 with fixed-order sums; ``n_usable`` is one
+    float64 on the device.  No finite logw: uniform weights, logw 0, ess P, degenerate 1 (pcnerf_mcl_weights).
+    Precondition: the ids are -1 .. B - 1 (assign_blocks' output); an id >= B is not known to be outside the map here
+    and keeps the finite weight of a pose that missed every beam."""
+    op = "mcl_weights"
+    _layout(op, "logw_prev", logw_prev, (("min", 1),), torch.float64)
+    Pn = logw_prev.shape[0]
+    if Pn > MCL_MAX_PARTICLES:
+        raise RuntimeError(f"pcnerf::{op}: {Pn} particles, at most {MCL_MAX_PARTICLES} are supported")
+    _layout(op, "scores4", scores4, (Pn, 4), torch.float64)
+    _layout(op, "block_of_pose", block_of_pose, (Pn,), torch.int32)
+    _layout(op, "n_usable", n_usable, (1,), torch.float64)
+    _need_on_device(op, logw_prev, scores4, block_of_pose, n_usable)
+    dev = logw_prev.device
+    w = torch.empty((Pn,), dtype=torch.float64, device=dev)
+    logw = torch.empty((Pn,), dtype=torch.float64, device=dev)
+    ess = torch.empty((1,), dtype=torch.float64, device=dev)
+    best = torch.empty((1,), dtype=torch.int32, device=dev)
+    deg = torch.empty((1,), dtype=torch.int32, device=dev)
+    nbytes = int(H.lib().pcnerf_mcl_weights_workspace_bytes(Pn))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_mcl_weights(logw_prev.data_ptr(), scores4.data_ptr(), block_of_pose.data_ptr(), Pn,
+                                       n_usable.data_ptr(), float(miss_cost), float(beta), ws.data_ptr(), nbytes,
+                                       w.data_ptr(), logw.data_ptr(), ess.data_ptr(), best.data_ptr(), deg.data_ptr(),
+                                       H.stream_of(logw_prev)))
+    return w, logw, ess, best, deg
+
+
+@mcl_weights.register_fake
+def _(logw_prev, scores4, block_of_pose, n_usable, miss_cost, beta):
+    Pn = logw_prev.shape[0]
+    return (logw_prev.new_empty((Pn,)), logw_prev.new_empty((Pn,)), logw_prev.new_empty((1,)),
+            logw_prev.new_empty((1,), dtype=torch.int32), logw_prev.new_empty((1,), dtype=torch.int32))
+
+
+@torch.library.custom_op(f"{NS}::systematic_resample", mutates_args=())
+def systematic_resample(w: Tensor, u0: Tensor, n_out: int, ess: Optional[Tensor], ess_threshold: float,
+                        poses12: Optional[Tensor], block_of_pose: Optional[Tensor],
+                        logw: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(ancestors (n_out,) int32, poses12_out (n_out, 12), blocks_out (n_out,) int32, logw_out (n_out,) float64; (0,)
+    where the input is None) of systematic resampling of the weights w (P,) float64 with the offset u0 (1,) float64 in
+    [0, 1) on the device: ancestor j is the first i whose inclusive prefix sum exceeds (j + u0) / n_out * sum(w),
+    never an i with w_i == 0.  With ``ess`` (mcl_weights' (1,) output; the ESS switch, n_out == P) and
+    ess >= ess_threshold, decided on the device, nothing is resampled: the identity, the log-weights kept; otherwise
+    the new log-weights are 0 (pcnerf_systematic_resample)."""
+    op = "systematic_resample"
+    _layout(op, "w", w, (("min", 1),), torch.float64)
+    Pn = w.shape[0]
+    if Pn > MCL_MAX_PARTICLES:
+        raise RuntimeError(f"pcnerf::{op}: {Pn} particles, at most {MCL_MAX_PARTICLES} are supported")
+    _layout(op, "u0", u0, (1,), torch.float64)
+    if n_out < 1:
+        raise RuntimeError(f"pcnerf::{op}: n_out = {n_out}, at least one draw is needed")
+    if ess is not None:
+        _layout(op, "ess", ess, (1,), torch.float64)
+        if n_out != Pn:
+            raise RuntimeError(f"pcnerf::{op}: n_out = {n_out} != P = {Pn} with the ESS switch on (the identity needs "
+                               "equal counts)")
+    if poses12 is not None:
+        _layout(op, "poses12", poses12, (Pn, 12), torch.float64)
+    if block_of_pose is not None:
+        _layout(op, "block_of_pose", block_of_pose, (Pn,), torch.int32)
+    if logw is not None:
+        _layout(op, "logw", logw, (Pn,), torch.float64)
+    _need_on_device(op, w, u0, ess, poses12, block_of_pose, logw)
+    dev = w.device
+    anc = torch.empty((n_out,), dtype=torch.int32, device=dev)
+    pout = torch.empty((n_out, 12) if poses12 is not None else (0,), dtype=torch.float64, device=dev)
+    bout = torch.empty((n_out,) if block_of_pose is not None else (0,), dtype=torch.int32, device=dev)
+    lout = torch.empty((n_out,) if logw is not None else (0,), dtype=torch.float64, device=dev)
+    nbytes = int(H.lib().pcnerf_systematic_resample_workspace_bytes(Pn))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_systematic_resample(w.data_ptr(), Pn, u0.data_ptr(), int(n_out), H.ptr(ess),
+                                               float(ess_threshold), H.ptr(poses12), H.ptr(block_of_pose),
+                                               H.ptr(logw), ws.data_ptr(), nbytes, anc.data_ptr(),
+                                               pout.data_ptr() if poses12 is not None else None,
+                                               bout.data_ptr() if block_of_pose is not None else None,
+                                               lout.data_ptr() if logw is not None else None, H.stream_of(w)))
+    return anc, pout, bout, lout
+
+
+@systematic_resample.register_fake
+def _(w, u0, n_out, ess, ess_threshold, poses12, block_of_pose, logw):
+    return (w.new_empty((n_out,), dtype=torch.int32),
+            w.new_empty((n_out, 12) if poses12 is not None else (0,), dtype=torch.float64),
+            w.new_empty((n_out,) if block_of_pose is not None else (0,), dtype=torch.int32),
+            w.new_empty((n_out,) if logw is not None else (0,), dtype=torch.float64))
+
+
+def map_op_names() -> list:
+    """The operators of the map and particle-filter layer (tests)."""
+    return ["assign_blocks", "score_poses_map", "pose_normal_eq_map", "refine_poses_map", "mcl_weights",
+            "systematic_resample"]

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import _torch_ops
-from .registration import (EPSILON, RegistrationResult, _check_frozen, refine_poses_fold, register_scan_fold,
-                           se3_exp)
+from .registration import (EPSILON, RegistrationResult, _block_ids, _check_frozen, refine_poses_fold,
+                           refine_poses_map, register_scan_fold, se3_exp)
 
 P = torch.ops.pcnerf
 
@@ -204,6 +204,13 @@ def _localize_batched(fold_c, fold_f, points_sensor, T_host, order, parent_lo, p
     the end, then the sequential path's winner rule on the host."""
     idx = torch.as_tensor(np.asarray(order, dtype=np.int64))
     r = refine_poses_fold(fold_c, fold_f, points_sensor, T_host[idx], parent_lo, parent_hi, iters=refine_iters, **kw)
+    best, refined = _winner_of_refined(r, order, same_basin_tol, mc, n_usable)
+    return LocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined)
+
+
+def _winner_of_refined(r, order, same_basin_tol, mc, n_usable):
+    """The sequential path's winner rule on a RefineResult of the candidates ``order`` (one read-back) ->
+    ((final mean cost, hypothesis index, RegistrationResult), refined list)."""
     poses, status = r.poses.cpu(), r.status.cpu().tolist()
     n_valid, iterations = r.n_valid.cpu().tolist(), r.iterations.cpu().tolist()
     eval_costs, mask = r.eval_costs.cpu(), r.accepted_mask.cpu()
@@ -222,7 +229,7 @@ def _localize_batched(fold_c, fold_f, points_sensor, T_host, order, parent_lo, p
     if best is None:
         raise RuntimeError("localize_scan: no candidate is left after the refinement (fewer than 6 valid beams or a "
                            "singular solve for each)")
-    return LocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined)
+    return best, refined
 
 
 def localize_scan(model_coarse, model_fine, points_sensor: torch.Tensor, poses, parent_lo, parent_hi, *,
@@ -235,3 +242,132 @@ def localize_scan(model_coarse, model_fine, points_sensor: torch.Tensor, poses, 
     fold_c, fold_f = _folds(model_coarse, model_fine)
     return localize_scan_fold(fold_c, fold_f, points_sensor, poses, parent_lo, parent_hi, top_k=top_k,
                               miss_cost=miss_cost, refine_iters=refine_iters, **render_kw)
+
+
+# ----------------------------------------------------------------------------------------------- maps of blocks
+# A PC-NeRF map is several parent blocks, each with its own pair of networks and its own AABB.  Every pose is rendered
+# against exactly one block -- its own -- and a beam is clipped where it leaves that block's box: nothing is composited
+# across blocks.  A block's AABB encloses the scans it was built from, so the sensor's own block sees the scene.
+class BlockMap:
+    """B >= 1 parent blocks on the device: ``folds_c`` / ``folds_f`` (B, 64) float64 (row b = pcnerf::fold_eval's
+    output of block b's coarse / fine network) and ``boxes`` (B, 6) float64 rows [lo, hi].  Boxes may overlap."""
+
+    def __init__(self, folds_c: torch.Tensor, folds_f: torch.Tensor, boxes: torch.Tensor):
+        fc, ff, bx = (torch.as_tensor(t).detach() for t in (folds_c, folds_f, boxes))
+        if not (fc.is_cuda and ff.is_cuda and bx.is_cuda):
+            raise RuntimeError("BlockMap holds device tensors; move the folds and boxes with .to('cuda') -- there is "
+                               "no CPU path")
+        if fc.dim() != 2 or fc.shape[0] < 1 or fc.shape[1] != 64 or tuple(ff.shape) != tuple(fc.shape):
+            raise RuntimeError(f"BlockMap: folds must be (B, 64) with B >= 1; got {tuple(fc.shape)} and "
+                               f"{tuple(ff.shape)}")
+        if tuple(bx.shape) != (fc.shape[0], 6):
+            raise RuntimeError(f"BlockMap: boxes must be (B, 6) with B = {fc.shape[0]}; got {tuple(bx.shape)}")
+        self.folds_c = fc.to(torch.float64).contiguous()
+        self.folds_f = ff.to(torch.float64).contiguous()
+        self.boxes = bx.to(torch.float64).contiguous()
+        self._boxes_host = self.boxes.cpu().numpy()   # (one copy at construction: default_miss_cost reads it)
+
+    @property
+    def n_blocks(self) -> int:
+        return int(self.boxes.shape[0])
+
+    @property
+    def device(self):
+        return self.boxes.device
+
+    @classmethod
+    def from_models(cls, blocks) -> "BlockMap":
+        """From [(model_coarse, model_fine, lo, hi), ...]: the frozen eval-mode networks of every block are folded once
+        (a train-mode module and parameters that require grad raise, as in score_poses)."""
+        blocks = list(blocks)
+        if not blocks:
+            raise RuntimeError("BlockMap.from_models: no blocks")
+        fcs, ffs, boxes = [], [], []
+        for mc, mf, lo, hi in blocks:
+            fc, ff = _folds(mc, mf)
+            fcs.append(fc)
+            ffs.append(ff)
+            boxes.append(np.concatenate([np.asarray(lo, dtype=np.float64).reshape(3),
+                                         np.asarray(hi, dtype=np.float64).reshape(3)]))
+        dev = fcs[0].device
+        return cls(torch.stack(fcs), torch.stack(ffs), torch.as_tensor(np.stack(boxes)).to(dev))
+
+    def default_miss_cost(self, huber_delta: float = 0.0) -> float:
+        """The largest ``default_miss_cost`` over the blocks: no block's valid beam can be charged more than a miss."""
+        return max(default_miss_cost(b[:3], b[3:], huber_delta) for b in self._boxes_host)
+
+
+class MapLocalizationResult(NamedTuple):
+    pose: torch.Tensor      # (4, 4) float64, host: the refined candidate with the lowest final mean cost
+    score: float            # its final mean cost
+    index: int              # the hypothesis it was refined from
+    scores: torch.Tensor    # (P,) float64, device: every hypothesis' mean cost
+    refined: list           # RegistrationResult of the top_k hypotheses, best hypothesis score first
+    block: int              # the winner's block
+    blocks: torch.Tensor    # (P,) int32, device: every hypothesis' block (-1: none)
+
+
+def assign_blocks(block_map: BlockMap, poses, margin: float = 0.0) -> torch.Tensor:
+    """(P,) int32 on the device: per pose (P, 4, 4, host or device) the block whose box contains its translation with
+    ``margin`` to spare on every side -- among several the one with the largest clearance
+    min_m min(t_m - lo_m, hi_m - t_m), the lowest index on ties -- or -1 when none does or the translation has a
+    NaN (``torch.ops.pcnerf.assign_blocks``, float64)."""
+    return P.assign_blocks(_poses12(poses, block_map.device), block_map.boxes, float(margin))
+
+
+def _scan_points(points_sensor: torch.Tensor) -> torch.Tensor:
+    if not points_sensor.is_cuda:
+        raise RuntimeError("nof.localization renders device-resident scans; move points_sensor with .to('cuda') -- "
+                           "there is no CPU path")
+    if points_sensor.dim() != 2 or points_sensor.shape[1] != 3:
+        raise RuntimeError(f"points_sensor must be (R, 3); got {tuple(points_sensor.shape)}")
+    return points_sensor.detach().float().contiguous()
+
+
+def score_poses_map(block_map: BlockMap, points_sensor: torch.Tensor, poses, blocks=None, *, N_samples: int = 64,
+                    N_importance: int = 128, huber_delta: float = 0.0, min_sumw: float = 0.5, near: float = 0.05,
+                    want_depth: bool = False) -> PoseScores:
+    """score_poses_fold against a map of blocks: pose p is rendered against block ``blocks[p]`` ((P,) integers, -1 for
+    none; None: ``assign_blocks``), the whole set in one launch (``torch.ops.pcnerf.score_poses_map``).  Every pose
+    scores the bits score_poses_fold gives with its block alone.  A pose without a block (-1, or an index outside the
+    map) renders nothing: zero sums, and NaN depth and zero sumw with ``want_depth``."""
+    pts = _scan_points(points_sensor)
+    _torch_ops.check_score_samples("score_poses_map", int(N_samples), int(N_importance))
+    rows = _poses12(poses, pts.device)
+    ids = _block_ids(block_map, rows, blocks)
+    s4, depth, sumw = P.score_poses_map(pts, rows, ids, block_map.boxes, block_map.folds_c, block_map.folds_f,
+                                        float(near), int(N_samples), int(N_importance), EPSILON, float(huber_delta),
+                                        float(min_sumw), bool(want_depth))
+    cost, n_valid, abs_r, hit = s4.t().contiguous()
+    return PoseScores(cost, n_valid.round().to(torch.int64), abs_r, hit, depth if want_depth else None,
+                      sumw if want_depth else None)
+
+
+def localize_scan_map(block_map: BlockMap, points_sensor: torch.Tensor, poses, *, top_k: int = 4,
+                      miss_cost: Optional[float] = None, refine_iters: int = 20, same_basin_tol=(1e-3, 1e-3),
+                      N_samples: int = 64, N_importance: int = 128, huber_delta: float = 0.0, min_sumw: float = 0.5,
+                      near: float = 0.05, blocks=None) -> MapLocalizationResult:
+    """localize_scan_fold over a map of blocks: every hypothesis is scored against its own block (``blocks``, or
+    ``assign_blocks`` at margin 0) in one launch, the ``top_k`` lowest mean costs are refined in one
+    ``refine_poses_map`` call against the blocks they were scored in, and localize_scan_fold's batched winner rule picks the basin.  A
+    hypothesis without a block is charged ``miss_cost`` for every usable beam; ``miss_cost`` defaults to the map's
+    ``default_miss_cost`` (the largest over the blocks).  Returns the winner's block as well."""
+    kw = dict(N_samples=N_samples, N_importance=N_importance, huber_delta=huber_delta, min_sumw=min_sumw, near=near)
+    T = torch.as_tensor(poses, dtype=torch.float64).detach()
+    pts = _scan_points(points_sensor)
+    ids = _block_ids(block_map, _poses12(T, pts.device), blocks)
+    s = score_poses_map(block_map, pts, T, ids, **kw)
+    if s.cost.shape[0] == 0:
+        raise RuntimeError("localize_scan: no hypotheses")
+    rng = torch.linalg.norm(points_sensor.detach().double(), dim=-1).float()
+    n_usable = int((torch.isfinite(rng) & (rng > 0)).sum())
+    if n_usable == 0:
+        raise RuntimeError("localize_scan: the scan has no beam with a finite range > 0")
+    mc = block_map.default_miss_cost(huber_delta) if miss_cost is None else float(miss_cost)
+    scores = (s.cost + mc * (n_usable - s.n_valid).double()) / n_usable
+    order = np.argsort(scores.cpu().numpy(), kind="stable")[:max(1, int(top_k))]
+    idx = torch.as_tensor(np.asarray(order, dtype=np.int64))
+    ids_host = ids.cpu()
+    r = refine_poses_map(block_map, pts, T.cpu()[idx], ids_host[idx], iters=int(refine_iters), **kw)
+    best, refined = _winner_of_refined(r, order, same_basin_tol, mc, n_usable)
+    return MapLocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined, int(ids_host[best[1]]), ids)

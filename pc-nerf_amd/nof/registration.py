@@ -328,3 +328,42 @@ def apply_twists(poses: torch.Tensor, xi: torch.Tensor) -> torch.Tensor:
     if x.dim() != 2 or tuple(x.shape) != (rows.shape[0], 6):
         raise RuntimeError(f"xi must be (P, 6) with P = {rows.shape[0]}; got {tuple(x.shape)}")
     return _rows_to_poses(P.se3_apply(x, rows))
+
+
+def _block_ids(block_map, rows: torch.Tensor, blocks) -> torch.Tensor:
+    """(P,) int32 device block ids of the (P, 12) pose rows: the caller's, or pcnerf::assign_blocks' at margin 0 (for
+    another margin, call assign_blocks and pass its result)."""
+    if blocks is None:
+        return P.assign_blocks(rows, block_map.boxes, 0.0)
+    b = torch.as_tensor(blocks).detach().to(device=rows.device, dtype=torch.int32).contiguous()
+    if tuple(b.shape) != (rows.shape[0],):
+        raise RuntimeError(f"blocks must be (P,) with P = {rows.shape[0]}; got {tuple(b.shape)}")
+    return b
+
+
+def refine_poses_map(block_map, points_sensor: torch.Tensor, poses, blocks=None, *, N_samples: int = 64,
+                     N_importance: int = 128, iters: int = 20, huber_delta: float = 0.0, min_sumw: float = 0.5,
+                     damping: float = 1e-6, near: float = 0.05, xi_tol: float = 1e-9) -> RefineResult:
+    """refine_poses_fold against a map of blocks (``nof.localization.BlockMap``): pose p is refined against block
+    ``blocks[p]`` ((P,) integers, -1 for none; None: ``assign_blocks`` of the start poses), in one call for the whole
+    set (``torch.ops.pcnerf.refine_poses_map``).  Every pose refines to the bits refine_poses_fold gives with its
+    block alone.  The block of a pose is fixed for the call: a pose that leaves its box on the way behaves as in the
+    single-block solver (its beams are clipped by the box it started in), and blocks are not re-assigned between
+    evaluations.  A pose without a block stops with status 2 at the first update and returns its input."""
+    if not points_sensor.is_cuda:
+        raise RuntimeError("nof.registration renders device-resident scans; move points_sensor with .to('cuda') -- "
+                           "there is no CPU path")
+    if points_sensor.dim() != 2 or points_sensor.shape[1] != 3:
+        raise RuntimeError(f"points_sensor must be (R, 3); got {tuple(points_sensor.shape)}")
+    _torch_ops.check_score_samples("refine_poses_map", int(N_samples), int(N_importance))
+    dev = points_sensor.device
+    pts = points_sensor.detach().float().contiguous()
+    rows_in = _pose_rows(poses, dev)
+    ids = _block_ids(block_map, rows_in, blocks)
+    rows, state, costs, acc = P.refine_poses_map(pts, rows_in, ids, block_map.boxes, block_map.folds_c,
+                                                 block_map.folds_f, float(near), int(N_samples), int(N_importance),
+                                                 EPSILON, float(huber_delta), float(min_sumw), float(damping),
+                                                 float(xi_tol), int(iters))
+    as_int = lambda c: state[:, c].round().to(torch.int64)   # noqa: E731
+    return RefineResult(_rows_to_poses(rows), state[:, 24 + 27].clone(), as_int(24 + 28), as_int(56), as_int(57),
+                        as_int(55), costs, acc.bool(), state[:, 54].clone(), state)
