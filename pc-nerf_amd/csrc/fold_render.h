@@ -1,5 +1,5 @@
 // The folded scan render shared by register.hip (k_render_jac_fold, k_gn_normal_eq), localize.hip
-// (k_score_poses_fold) and refine.hip (k_pose_normal_eq_fold): one wave renders one ray through the folded eval
+// (k_score_poses) and refine.hip (k_pose_normal_eq): one wave renders one ray through the folded eval
 // network p = sigmoid(a . e(x) + c) (fold_dot, pcnerf_internal.h).  The three kernels must agree
 // bit for bit on depth, sumw and jac6 (the tests compare them with the composed route), so every step they share is
 // defined here once:
@@ -25,7 +25,8 @@
 //                         sort(cat(zc, draws)).  The merged list aliases the weights and the cdf, dead by then;
 //   gn_*               6. the per-beam Gauss-Newton pieces: the validity rule, the pose Jacobian
 //                         Jp = [J_o, o x J_o + d x J_d] of the left perturbation T' = exp(xi) T (delta o = rho + phi x o,
-//                         delta d = phi x d), the Huber weight and cost term.  Each kernel keeps its own accumulation.
+//                         delta d = phi x d), the Huber weight and cost term.  Each kernel keeps its own accumulation;
+//   fr_block_of        which block of a map a pose of the two pose kernels is rendered against.
 // Loops are bounded by S and I (the binary searches by their logarithm), never by data, and every LDS index is clamped,
 // so NaN rays (rng == 0, a non-finite point) cost time but cannot leave their slice.
 // Host side: the LDS slice size, the blocks per pose, the sample-count checks and the MAXB dispatch of the launchers.
@@ -37,6 +38,13 @@
 namespace pcn {
 
 constexpr int FR_MAX_S = 1024;   // 64 lanes x 16 samples per lane (the two-pass kernels' fine pass: S + I)
+
+// The block of a pose in a map of n_blocks, or -1 for "no block": never index with anything else.  (The single-block
+// entries have no table: their kernels are compiled with block 0 for every pose and do not call this.)
+__device__ __forceinline__ int fr_block_of(const int* __restrict__ block_of_pose, int64_t pose, int n_blocks) {
+  const int b = block_of_pose[pose];
+  return (b >= 0 && b < n_blocks) ? b : -1;
+}
 
 // One render pass of the wave's ray `row` (o, d) over the n depths zs (LDS or global memory), B = ceil(n / 64) <= MAXB:
 // dep and hit in float64 (every lane the same values); w_out (the n normalised weights) or NULL.  JAC: the samples

@@ -1,50 +1,69 @@
 // Pose-hypothesis scoring against folded eval networks: the whole two-pass render of a scan (rays from the pose,
 // coarse depths, coarse pass, deterministic resampling, fine pass) and the per-pose reduction of the range residuals
-// in one launch, with nothing per sample through memory.  The numbered steps are fold_render.h's, shared with
-// refine.hip and register.hip.
+// in one launch, with nothing per sample through memory.  Every pose is rendered against ITS OWN block of a map of B
+// blocks (its pair of fold vectors and its box); a single block is the map with B = 1 in which every pose has block
+// 0, and is the same kernel body with that written in at compile time (MAP = false).  The numbered steps are
+// fold_render.h's, shared with refine.hip and register.hip.
 //
-//   k_score_poses_fold<MAXB>  one wave per (pose, beam), four beams per 256-thread workgroup, ceil(R / 4) workgroups
-//                             per pose (a workgroup never straddles two poses).  Both fold vectors, the workgroup's
-//                             pose, the box and the loss parameters sit in LDS (as scalars they spilled SGPRs).  Per
-//                             wave, in its own LDS slice zc (S) | fs (I) | max(2 S, S + I) floats:
-//                               1. the world ray (fr_pose_ray);
-//                               2. zc = k_sample_coarse's plain path, lerp_z(near, far, linspace01(i, S));
-//                               3. the coarse pass (fr_pass), the normalised weights rounded once to float32 into LDS;
-//                               4. fr_resample_merge;
-//                               5. the fine pass on the S + I merged depths -> depth, sumw, each rounded once;
-//                               6. r = depth - rng on the float32 values, rho(r) as k_gn_normal_eq's cost term.
-//                             The two passes share one rolled loop, so there is a single copy of the pass: the scalar
-//                             register file is full, and unrolled forms spilled it.  The four waves' terms (rho, 1,
-//                             |r| over the valid beams; sumw over the usable ones) are added in wave order into one
-//                             4-double partial per workgroup.
-//   k_score_poses_sum         one workgroup per pose adds its ceil(R / 4) partials: 64 chains (partials q, q + 64,
-//                             ...), then a fixed tree.
+//   k_score_poses<MAXB, MAP>
+//                        one wave per (pose, beam), four beams per 256-thread workgroup, ceil(R / 4) workgroups per
+//                        pose.  A workgroup never straddles two poses, so its prologue takes the pose's block b
+//                        (MAP: fr_block_of, uniform; the single-block entry compiles b = 0 in) and stages folds_c[b],
+//                        folds_f[b], boxes[b], the pose and the loss parameters through LDS (as scalars they spilled
+//                        SGPRs).  An index outside 0 .. B - 1 renders nothing: the workgroup writes its zero partial
+//                        (and NaN depth, zero sumw when asked for) and returns before the first barrier; nothing is
+//                        indexed with it.  Per wave, in its own LDS slice zc (S) | fs (I) | max(2 S, S + I) floats:
+//                          1. the world ray (fr_pose_ray);
+//                          2. zc = k_sample_coarse's plain path, lerp_z(near, far, linspace01(i, S));
+//                          3. the coarse pass (fr_pass), the normalised weights rounded once to float32 into LDS;
+//                          4. fr_resample_merge;
+//                          5. the fine pass on the S + I merged depths -> depth, sumw, each rounded once;
+//                          6. r = depth - rng on the float32 values, rho(r) as k_gn_normal_eq's cost term.
+//                        The two passes share one rolled loop, so there is a single copy of the pass: the scalar
+//                        register file is full, and unrolled forms spilled it.  The four waves' terms (rho, 1, |r|
+//                        over the valid beams; sumw over the usable ones) are added in wave order into one 4-double
+//                        partial per workgroup.
+//   k_score_poses_sum    one workgroup per pose adds its ceil(R / 4) partials: 64 chains (partials q, q + 64, ...),
+//                        then a fixed tree.
+// pcnerf_score_poses_fold (no table, B = 1, its one box and pair of folds) and pcnerf_score_poses_map are thin entries
+// over one host function.  Beams are clipped at their block's box exit; there is no compositing across blocks.
 // No atomics, every output word has one writer, and geometry and summation order depend on (P, R) alone: a pose scores
-// the same bits alone or in a batch, with or without the per-beam outputs.  NaN rays are not counted.
+// the same bits alone or in a batch, with or without the per-beam outputs, as block b of a map or against block b
+// alone.  NaN rays are not counted.
 #include "fold_render.h"
 
 namespace pcn {
 
 constexpr int SP_W = 4;   // doubles per partial and per pose: cost, n_valid, sum |r|, sum sumw
 
-template <int MAXB>
-__global__ __launch_bounds__(256) void k_score_poses_fold(
-    const float* __restrict__ points, int64_t n_beams, const double* __restrict__ poses12, int bpp,
-    const double* __restrict__ box6, float near, int S, int I, const double* __restrict__ fold_c,
-    const double* __restrict__ fold_f, float eps, double delta_arg, double min_sumw_arg, double* __restrict__ part,
-    float* __restrict__ depth_out, float* __restrict__ sumw_out) {
+template <int MAXB, bool MAP>
+__global__ __launch_bounds__(256) void k_score_poses(
+    const float* __restrict__ points, int64_t n_beams, const double* __restrict__ poses12,
+    const int* __restrict__ block_of_pose, int n_blocks, int bpp, const double* __restrict__ boxes6, float near, int S,
+    int I, const double* __restrict__ folds_c, const double* __restrict__ folds_f, float eps, double delta_arg,
+    double min_sumw_arg, double* __restrict__ part, float* __restrict__ depth_out, float* __restrict__ sumw_out) {
   extern __shared__ float sp_lds[];
   __shared__ double fa[2][64];
   __shared__ double red[4][SP_W];
   __shared__ double pb[20];   // [R row-major (9), t (3), lo (3), hi (3), huber_delta, min_sumw]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t pose = blockIdx.x / (unsigned)bpp;
-  if (tid < 128) fa[tid >> 6][lane] = (tid < 64 ? fold_c : fold_f)[lane];
+  const int64_t beam = (int64_t)(blockIdx.x - (unsigned)pose * (unsigned)bpp) * 4 + wave;
+  const int b = MAP ? fr_block_of(block_of_pose, pose, n_blocks) : 0;
+  if (MAP && b < 0) {   // (uniform across the workgroup, before the first barrier)
+    if (tid < SP_W) part[(int64_t)blockIdx.x * SP_W + tid] = 0.0;
+    if (lane == 0 && beam < n_beams) {
+      const int64_t g = pose * n_beams + beam;
+      if (depth_out) depth_out[g] = __builtin_nanf("");
+      if (sumw_out) sumw_out[g] = 0.0f;
+    }
+    return;
+  }
+  if (tid < 128) fa[tid >> 6][lane] = (tid < 64 ? folds_c : folds_f)[64 * b + lane];
   else if (tid < 140) pb[tid - 128] = poses12[12 * pose + (tid - 128)];   // the workgroup's pose and the box through
-  else if (tid < 146) pb[tid - 128] = box6[tid - 140];                    // LDS: vector registers, not 36 scalar ones
+  else if (tid < 146) pb[tid - 128] = boxes6[6 * b + (tid - 140)];        // LDS: vector registers, not 36 scalar ones
   else if (tid < 148) pb[tid - 128] = tid == 146 ? delta_arg : min_sumw_arg;   // (needed last: not held in scalars)
   __syncthreads();
-  const int64_t beam = (int64_t)(blockIdx.x - (unsigned)pose * (unsigned)bpp) * 4 + wave;
   double term[SP_W] = {0.0, 0.0, 0.0, 0.0};
   if (beam < n_beams) {   // (wave-uniform: the shuffles below always have 64 lanes)
     float* zc = sp_lds + (size_t)wave * fr_slice_floats(S, I);
@@ -117,6 +136,43 @@ __global__ __launch_bounds__(256) void k_score_poses_sum(const double* __restric
   if (q == 0) scores4[(int64_t)blockIdx.x * SP_W + f] = red[0][f];
 }
 
+// Both entries: `name` prefixes the error texts; with_table: the map entry, whose block_of_pose must be given
+int sp_score_poses(const char* name, bool with_table, const float* points, int64_t n_beams, const double* poses12,
+                   int64_t n_poses, const int* block_of_pose, int n_blocks, const double* boxes6, float near, int S,
+                   int I, const double* folds_c, const double* folds_f, float eps, double huber_delta, double min_sumw,
+                   void* workspace, size_t workspace_bytes, double* scores4, float* depth_or_null, float* sumw_or_null,
+                   hipStream_t stream) {
+  PCN_API_BEGIN
+  const std::string who(name);
+  PCN_CHECK(n_poses >= 0 && n_beams >= 0, who + ": negative count");
+  fr_check_samples(name, S, I);
+  if (n_poses == 0) return 0;
+  PCN_CHECK(scores4, who + ": null argument");
+  if (n_beams == 0) {
+    PCN_HIP(hipMemsetAsync(scores4, 0, (size_t)n_poses * SP_W * sizeof(double), stream));
+    return 0;
+  }
+  PCN_CHECK(points && poses12 && (block_of_pose || !with_table) && boxes6 && folds_c && folds_f && workspace,
+            who + ": null argument");
+  PCN_CHECK(n_blocks >= 1, who + ": n_blocks < 1");
+  PCN_CHECK(workspace_bytes >= pcnerf_score_poses_workspace_bytes(n_poses, n_beams),
+            who + ": workspace smaller than pcnerf_score_poses_workspace_bytes");
+  fr_check_pairs(name, n_poses, n_beams);
+  const int64_t bpp = fr_blocks_per_pose(n_beams);
+  const size_t lds = (size_t)4 * fr_slice_floats(S, I) * sizeof(float);   // <= 48 KiB
+  double* part = reinterpret_cast<double*>(workspace);
+  fr_dispatch_maxb(S + I, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    const auto kernel = with_table ? &k_score_poses<MB, true> : &k_score_poses<MB, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_poses * bpp)), dim3(256), lds, stream, points, n_beams, poses12,
+                       block_of_pose, n_blocks, (int)bpp, boxes6, near, S, I, folds_c, folds_f, eps, huber_delta,
+                       min_sumw, part, depth_or_null, sumw_or_null);
+  });
+  hipLaunchKernelGGL(k_score_poses_sum, dim3((unsigned)n_poses), dim3(256), 0, stream, part, (int)bpp, scores4);
+  PCN_LAUNCH_CHECK(name);
+  PCN_API_END_NEG
+}
+
 }  // namespace pcn
 
 using namespace pcn;
@@ -132,31 +188,19 @@ extern "C" int pcnerf_score_poses_fold(const float* points_sensor, int64_t n_bea
                                        float eps, double huber_delta, double min_sumw, void* workspace,
                                        size_t workspace_bytes, double* scores4, float* depth_or_null,
                                        float* sumw_or_null, void* stream) {
-  PCN_API_BEGIN
-  PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_score_poses_fold: negative count");
-  fr_check_samples("pcnerf_score_poses_fold", n_samples, n_importance);
-  if (n_poses == 0) return 0;
-  PCN_CHECK(scores4, "pcnerf_score_poses_fold: null argument");
-  if (n_beams == 0) {
-    PCN_HIP(hipMemsetAsync(scores4, 0, (size_t)n_poses * SP_W * sizeof(double), (hipStream_t)stream));
-    return 0;
-  }
-  PCN_CHECK(points_sensor && poses12 && parent_box6 && fold_coarse && fold_fine && workspace,
-            "pcnerf_score_poses_fold: null argument");
-  PCN_CHECK(workspace_bytes >= pcnerf_score_poses_workspace_bytes(n_poses, n_beams),
-            "pcnerf_score_poses_fold: workspace smaller than pcnerf_score_poses_workspace_bytes");
-  fr_check_pairs("pcnerf_score_poses_fold", n_poses, n_beams);
-  const int64_t bpp = fr_blocks_per_pose(n_beams);
-  const size_t lds = (size_t)4 * fr_slice_floats(n_samples, n_importance) * sizeof(float);   // <= 48 KiB
-  double* part = reinterpret_cast<double*>(workspace);
-  fr_dispatch_maxb(n_samples + n_importance, [&](auto mb) {
-    hipLaunchKernelGGL(k_score_poses_fold<decltype(mb)::value>, dim3((unsigned)(n_poses * bpp)), dim3(256), lds,
-                       (hipStream_t)stream, points_sensor, n_beams, poses12, (int)bpp, parent_box6, near, n_samples,
-                       n_importance, fold_coarse, fold_fine, eps, huber_delta, min_sumw, part, depth_or_null,
-                       sumw_or_null);
-  });
-  hipLaunchKernelGGL(k_score_poses_sum, dim3((unsigned)n_poses), dim3(256), 0, (hipStream_t)stream, part, (int)bpp,
-                     scores4);
-  PCN_LAUNCH_CHECK("pcnerf_score_poses_fold");
-  PCN_API_END_NEG
+  return sp_score_poses("pcnerf_score_poses_fold", false, points_sensor, n_beams, poses12, n_poses, nullptr, 1,
+                        parent_box6, near, n_samples, n_importance, fold_coarse, fold_fine, eps, huber_delta, min_sumw,
+                        workspace, workspace_bytes, scores4, depth_or_null, sumw_or_null, (hipStream_t)stream);
+}
+
+extern "C" int pcnerf_score_poses_map(const float* points_sensor, int64_t n_beams, const double* poses12,
+                                      int64_t n_poses, const int32_t* block_of_pose, int n_blocks,
+                                      const double* boxes6, float near, int n_samples, int n_importance,
+                                      const double* folds_coarse, const double* folds_fine, float eps,
+                                      double huber_delta, double min_sumw, void* workspace, size_t workspace_bytes,
+                                      double* scores4, float* depth_or_null, float* sumw_or_null, void* stream) {
+  return sp_score_poses("pcnerf_score_poses_map", true, points_sensor, n_beams, poses12, n_poses, block_of_pose,
+                        n_blocks, boxes6, near, n_samples, n_importance, folds_coarse, folds_fine, eps, huber_delta,
+                        min_sumw, workspace, workspace_bytes, scores4, depth_or_null, sumw_or_null,
+                        (hipStream_t)stream);
 }

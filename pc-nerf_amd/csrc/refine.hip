@@ -1,28 +1,38 @@
 // Batched pose refinement against folded eval networks: damped Gauss-Newton (Levenberg-Marquardt) on the range
-// residuals of one scan for many poses at once, with no host synchronisation between evaluations.  An evaluation is
-// three launches in stream order:
+// residuals of one scan for many poses at once, with no host synchronisation between evaluations.  Every pose is
+// refined against ITS OWN block of a map of B blocks, fixed for the call; a single block is the map with B = 1 in
+// which every pose has block 0: the same kernel body with that written in at compile time (MAP = false).  An
+// evaluation is three launches in stream order:
 //
-//   k_pose_normal_eq_fold<MAXB>  k_score_poses_fold's layout (localize.hip): one wave per (pose, beam), four beams
-//                                per 256-thread workgroup, ceil(R / 4) workgroups per pose; folds, pose, box and loss
-//                                parameters through LDS; per wave an LDS slice zc (S) | draws (I) | weights + cdf,
-//                                aliased by the merged depths.  Steps 1-5 are fold_render.h's, the same bits of depth
-//                                and sumw as that kernel's; here two instantiations of the pass: the coarse one
-//                                carries no Jacobian, the fine one k_render_jac_fold's (register.hip).  Then
-//                                k_gn_normal_eq's terms on the float32 depth, sumw, jac6 and ray row, one term per
-//                                lane: 21 of H's upper triangle, 6 of b, rho(r) and 1.  The four waves' terms are
-//                                added in wave order into one 32-double partial per workgroup.  Nothing per sample
-//                                goes through memory.  A workgroup whose pose has status != 0 (the state the previous
-//                                launch wrote) returns before its first barrier; the test is uniform across the
-//                                workgroup.
-//   k_pose_normal_eq_sum         one workgroup per pose adds its ceil(R / 4) partials, eight chains (partials q,
-//                                q + 8, ...) and a fixed tree, into normal30[pose] (pcnerf_gn_normal_eq's out30); a
-//                                stopped pose's row is zeroed.
-//   k_lm_update                  one thread per pose, float64: nof.registration.register_scan_fold's state machine
-//                                (accept / reject, lambda / 10 or x 10, the 6 x 6 solve by elimination with partial
-//                                pivoting, T <- se3_exp(xi) T), kept fully in registers.
-//   k_se3_apply                  poses12_out[p] = se3_exp(xi[p]) poses12[p] with the same device function.
+//   k_pose_normal_eq<MAXB, MAP>
+//                           k_score_poses' layout (localize.hip): one wave per (pose, beam), four beams per
+//                           256-thread workgroup, ceil(R / 4) workgroups per pose; the folds and the box of the
+//                           pose's block (MAP: fr_block_of; the single-block entries compile b = 0 in), the pose and
+//                           the loss parameters through LDS; per wave an LDS slice zc (S) | draws (I) | weights +
+//                           cdf, aliased by the merged depths.  Steps 1-5 are fold_render.h's, the same bits of
+//                           depth and sumw as that kernel's; here two instantiations of the pass: the coarse one
+//                           carries no Jacobian, the fine one k_render_jac_fold's (register.hip).  Then
+//                           k_gn_normal_eq's terms on the float32 depth, sumw, jac6 and ray row, one term per lane:
+//                           21 of H's upper triangle, 6 of b, rho(r) and 1.  The four waves' terms are added in
+//                           wave order into one 32-double partial per workgroup.  Nothing per sample goes through
+//                           memory.  A workgroup whose pose has status != 0 (the state the previous launch wrote)
+//                           returns before its first barrier, and so does one whose pose has no block (an index
+//                           outside 0 .. B - 1, never used to index); both tests are uniform across the workgroup
+//                           and no partial is written.
+//   k_pose_normal_eq_sum    one workgroup per pose adds its ceil(R / 4) partials, eight chains (partials q, q + 8,
+//                           ...) and a fixed tree, into normal30[pose] (pcnerf_gn_normal_eq's out30); the row of a
+//                           stopped pose and of a pose without a block is zeroed, so k_lm_update stops the latter
+//                           with status 2 (zero valid beams) at the first update.
+//   k_lm_update             one thread per pose, float64: nof.registration.register_scan_fold's state machine
+//                           (accept / reject, lambda / 10 or x 10, the 6 x 6 solve by elimination with partial
+//                           pivoting, T <- se3_exp(xi) T), kept fully in registers.
+//   k_se3_apply             poses12_out[p] = se3_exp(xi[p]) poses12[p] with the same device function.
+// pcnerf_pose_normal_eq_fold / _map and pcnerf_refine_poses_fold / _map are thin entries over pn_normal_eq and
+// lm_refine_poses: the fold entries hand over no table, B = 1 and their one box and pair of folds.  Beams are clipped
+// at their block's box exit; there is no compositing across blocks.
 // No atomics, every output word has one writer, and geometry and summation order depend on (P, R) alone: a pose
-// refines to the same bits alone or in a batch, with or without the per-beam outputs.  NaN rays are not counted.
+// refines to the same bits alone or in a batch, with or without the per-beam outputs, as block b of a map or against
+// block b alone.  NaN rays are not counted.
 #include "fold_render.h"
 
 namespace pcn {
@@ -33,25 +43,27 @@ constexpr int LM_STATE = PCNERF_LM_STATE_DOUBLES;
 constexpr int LM_TACC = 0, LM_TTRIAL = 12, LM_N30 = 24, LM_LAMBDA = 54, LM_STATUS = 55, LM_EVALS = 56, LM_NACC = 57,
               LM_XI = 58;
 
-template <int MAXB>
-__global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
+template <int MAXB, bool MAP>
+__global__ __launch_bounds__(256) void k_pose_normal_eq(
     const float* __restrict__ points, int64_t n_beams, const double* __restrict__ poses12,
-    const double* __restrict__ state, int bpp, const double* __restrict__ box6, float near, int S, int I,
-    const double* __restrict__ fold_c, const double* __restrict__ fold_f, float eps, double delta_arg,
-    double min_sumw_arg, double* __restrict__ part, float* __restrict__ depth_out, float* __restrict__ sumw_out,
-    float* __restrict__ jac_out) {
+    const double* __restrict__ state, const int* __restrict__ block_of_pose, int n_blocks, int bpp,
+    const double* __restrict__ boxes6, float near, int S, int I, const double* __restrict__ folds_c,
+    const double* __restrict__ folds_f, float eps, double delta_arg, double min_sumw_arg, double* __restrict__ part,
+    float* __restrict__ depth_out, float* __restrict__ sumw_out, float* __restrict__ jac_out) {
   extern __shared__ float pn_lds[];
   __shared__ double fa[2][64];
   __shared__ double red[4][PN_W];
   __shared__ double pb[20];   // [R row-major (9), t (3), lo (3), hi (3), huber_delta, min_sumw]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t pose = blockIdx.x / (unsigned)bpp;
-  // a stopped pose costs nothing further (uniform across the workgroup, before the first barrier)
+  // a stopped pose and a pose without a block cost nothing further (uniform, before the first barrier)
   if (state && state[LM_STATE * pose + LM_STATUS] != 0.0) return;
+  const int b = MAP ? fr_block_of(block_of_pose, pose, n_blocks) : 0;
+  if (MAP && b < 0) return;
   const double* __restrict__ psrc = state ? state + LM_STATE * pose + LM_TTRIAL : poses12 + 12 * pose;
-  if (tid < 128) fa[tid >> 6][lane] = (tid < 64 ? fold_c : fold_f)[lane];
+  if (tid < 128) fa[tid >> 6][lane] = (tid < 64 ? folds_c : folds_f)[64 * b + lane];
   else if (tid < 140) pb[tid - 128] = psrc[tid - 128];
-  else if (tid < 146) pb[tid - 128] = box6[tid - 140];
+  else if (tid < 146) pb[tid - 128] = boxes6[6 * b + (tid - 140)];
   else if (tid < 148) pb[tid - 128] = tid == 146 ? delta_arg : min_sumw_arg;
   __syncthreads();
   const int64_t beam = (int64_t)(blockIdx.x - (unsigned)pose * (unsigned)bpp) * 4 + wave;
@@ -117,15 +129,17 @@ __global__ __launch_bounds__(256) void k_pose_normal_eq_fold(
 }
 
 // normal30[p][f] = sum_w part[p bpp + w][f]: thread (f, q) adds partials q, q + 8, ... in order, the eight chains in a
-// fixed tree.  A stopped pose's row is zeroed (its partials were not written).
+// fixed tree.  The row of a stopped pose or of a pose without a block is zeroed (its partials were not written).
 __global__ __launch_bounds__(256) void k_pose_normal_eq_sum(const double* __restrict__ part, int bpp,
                                                             const double* __restrict__ state,
+                                                            const int* __restrict__ block_of_pose, int n_blocks,
                                                             double* __restrict__ normal30) {
   __shared__ double red[8][PN_W];
   const int f = threadIdx.x & 31, q = threadIdx.x >> 5;
   const int64_t pose = blockIdx.x;
-  if (state && state[LM_STATE * pose + LM_STATUS] != 0.0) {   // (uniform across the workgroup)
-    if (threadIdx.x < 30) normal30[30 * pose + threadIdx.x] = 0.0;
+  if ((state && state[LM_STATE * pose + LM_STATUS] != 0.0) ||
+      (block_of_pose && fr_block_of(block_of_pose, pose, n_blocks) < 0)) {   // (no table: the single block)
+    if (threadIdx.x < 30) normal30[30 * pose + threadIdx.x] = 0.0;   // (uniform across the workgroup)
     return;
   }
   const double* __restrict__ pp = part + pose * bpp * PN_W;
@@ -358,12 +372,23 @@ size_t pn_workspace_bytes(int64_t n_poses, int64_t n_beams) {
   return (size_t)n_poses * (size_t)fr_blocks_per_pose(n_beams) * PN_W * sizeof(double);
 }
 
+// The map a call renders against.  The single-block entries pass {false, nullptr, 1, box, fold, fold}: block 0 of 1
+// for every pose (the MAP = false kernels); with_table: a map entry, whose block_of_pose must be given.
+struct PnMap {
+  bool with_table;
+  const int* block_of_pose;
+  int n_blocks;
+  const double *boxes6, *folds_c, *folds_f;
+};
+
 // every check an evaluation makes, before anything is launched (n_poses > 0)
-void pn_check_eval(const char* name, const float* points, int64_t n_beams, int64_t n_poses, const double* box6,
-                   const double* fold_c, const double* fold_f, void* workspace, size_t workspace_bytes) {
+void pn_check_eval(const char* name, const float* points, int64_t n_beams, int64_t n_poses, const PnMap& m,
+                   void* workspace, size_t workspace_bytes) {
   const std::string who(name);
   if (n_beams == 0) return;
-  PCN_CHECK(points && box6 && fold_c && fold_f && workspace, who + ": null argument");
+  PCN_CHECK(points && (m.block_of_pose || !m.with_table) && m.boxes6 && m.folds_c && m.folds_f && workspace,
+            who + ": null argument");
+  PCN_CHECK(m.n_blocks >= 1, who + ": n_blocks < 1");
   PCN_CHECK(workspace_bytes >= pn_workspace_bytes(n_poses, n_beams),
             who + ": workspace smaller than pcnerf_pose_normal_eq_workspace_bytes");
   fr_check_pairs(name, n_poses, n_beams);
@@ -371,9 +396,8 @@ void pn_check_eval(const char* name, const float* points, int64_t n_beams, int64
 
 // one evaluation of all running poses (checked by pn_check_eval); n_poses > 0
 void pn_launch_eval(const float* points, int64_t n_beams, const double* poses12, int64_t n_poses, const double* state,
-                    const double* box6, float near, int S, int I, const double* fold_c, const double* fold_f,
-                    float eps, double delta, double min_sumw, void* workspace, double* normal30, float* depth,
-                    float* sumw, float* jac6, hipStream_t stream) {
+                    const PnMap& m, float near, int S, int I, float eps, double delta, double min_sumw,
+                    void* workspace, double* normal30, float* depth, float* sumw, float* jac6, hipStream_t stream) {
   if (n_beams == 0) {
     PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), stream));
     return;
@@ -382,12 +406,68 @@ void pn_launch_eval(const float* points, int64_t n_beams, const double* poses12,
   const size_t lds = (size_t)4 * fr_slice_floats(S, I) * sizeof(float);   // <= 48 KiB
   double* part = reinterpret_cast<double*>(workspace);
   fr_dispatch_maxb(S + I, [&](auto mb) {
-    hipLaunchKernelGGL(k_pose_normal_eq_fold<decltype(mb)::value>, dim3((unsigned)(n_poses * bpp)), dim3(256), lds,
-                       stream, points, n_beams, poses12, state, (int)bpp, box6, near, S, I, fold_c, fold_f, eps, delta,
-                       min_sumw, part, depth, sumw, jac6);
+    constexpr int MB = decltype(mb)::value;
+    const auto kernel = m.with_table ? &k_pose_normal_eq<MB, true> : &k_pose_normal_eq<MB, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_poses * bpp)), dim3(256), lds, stream, points, n_beams, poses12,
+                       state, m.block_of_pose, m.n_blocks, (int)bpp, m.boxes6, near, S, I, m.folds_c, m.folds_f, eps,
+                       delta, min_sumw, part, depth, sumw, jac6);
   });
   hipLaunchKernelGGL(k_pose_normal_eq_sum, dim3((unsigned)n_poses), dim3(256), 0, stream, part, (int)bpp, state,
-                     normal30);
+                     m.block_of_pose, m.n_blocks, normal30);
+}
+
+// pcnerf_pose_normal_eq_fold and _map: `name` prefixes the error texts
+int pn_normal_eq(const char* name, const float* points, int64_t n_beams, const double* poses12_or_null,
+                 int64_t n_poses, const double* state_or_null, const PnMap& m, float near, int S, int I, float eps,
+                 double huber_delta, double min_sumw, void* workspace, size_t workspace_bytes, double* normal30,
+                 float* depth_or_null, float* sumw_or_null, float* jac6_or_null, hipStream_t stream) {
+  PCN_API_BEGIN
+  const std::string who(name);
+  PCN_CHECK(n_poses >= 0 && n_beams >= 0, who + ": negative count");
+  fr_check_samples(name, S, I);
+  if (n_poses == 0) return 0;
+  PCN_CHECK(normal30 && (poses12_or_null || state_or_null), who + ": null argument");
+  pn_check_eval(name, points, n_beams, n_poses, m, workspace, workspace_bytes);
+  pn_launch_eval(points, n_beams, poses12_or_null, n_poses, state_or_null, m, near, S, I, eps, huber_delta, min_sumw,
+                 workspace, normal30, depth_or_null, sumw_or_null, jac6_or_null, stream);
+  PCN_LAUNCH_CHECK(name);
+  PCN_API_END_NEG
+}
+
+// pcnerf_refine_poses_fold and _map: the init, iters x (evaluation, sum, update) and the pose output in stream order
+int lm_refine_poses(const char* name, const float* points, int64_t n_beams, const double* poses12, int64_t n_poses,
+                    const PnMap& m, float near, int S, int I, float eps, double huber_delta, double min_sumw,
+                    double damping, double xi_tol, int iters, void* workspace, size_t workspace_bytes,
+                    double* normal30, double* state, double* poses12_out, double* eval_costs, uint8_t* accepted,
+                    hipStream_t s) {
+  PCN_API_BEGIN
+  const std::string who(name);
+  PCN_CHECK(n_poses >= 0 && n_beams >= 0, who + ": negative count");
+  PCN_CHECK(iters >= 0, who + ": iters < 0");
+  fr_check_samples(name, S, I);
+  if (n_poses == 0) return 0;
+  PCN_CHECK(poses12 && normal30 && state && poses12_out, who + ": null argument");
+  PCN_CHECK(iters == 0 || (eval_costs && accepted), who + ": null argument");
+  PCN_CHECK(n_poses < (int64_t)1 << 31 && n_poses * ((int64_t)iters + LM_STATE) < (int64_t)1 << 37,
+            who + ": too many poses for one launch");   // (one thread per state / record word)
+  pn_check_eval(name, points, n_beams, n_poses, m, workspace, workspace_bytes);
+  if (n_beams == 0)   // (a refinement over a map wants its table even when no beam reads it)
+    PCN_CHECK(m.block_of_pose || !m.with_table, who + ": null argument");
+  hipLaunchKernelGGL(k_lm_init, dim3(lm_blocks(n_poses * LM_STATE)), dim3(64), 0, s, poses12, n_poses, damping,
+                     state);
+  PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), s));
+  if (iters > 0)
+    hipLaunchKernelGGL(k_lm_records_init, dim3(lm_blocks(n_poses * iters)), dim3(64), 0, s, n_poses * iters,
+                       eval_costs, accepted);
+  for (int it = 0; it < iters; ++it) {   // stream order is the only synchronisation between evaluations
+    pn_launch_eval(points, n_beams, nullptr, n_poses, state, m, near, S, I, eps, huber_delta, min_sumw, workspace,
+                   normal30, nullptr, nullptr, nullptr, s);
+    hipLaunchKernelGGL(k_lm_update, dim3(lm_blocks(n_poses)), dim3(64), 0, s, normal30, n_poses, xi_tol, state,
+                       eval_costs, accepted, it, iters);
+  }
+  hipLaunchKernelGGL(k_lm_poses_out, dim3(lm_blocks(n_poses * 12)), dim3(64), 0, s, state, n_poses, poses12_out);
+  PCN_LAUNCH_CHECK(name);
+  PCN_API_END_NEG
 }
 
 }  // namespace pcn
@@ -405,19 +485,23 @@ extern "C" int pcnerf_pose_normal_eq_fold(const float* points_sensor, int64_t n_
                                           void* workspace, size_t workspace_bytes, double* normal30,
                                           float* depth_or_null, float* sumw_or_null, float* jac6_or_null,
                                           void* stream) {
-  PCN_API_BEGIN
-  const char* who = "pcnerf_pose_normal_eq_fold";
-  PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_pose_normal_eq_fold: negative count");
-  fr_check_samples(who, n_samples, n_importance);
-  if (n_poses == 0) return 0;
-  PCN_CHECK(normal30 && (poses12_or_null || state_or_null), "pcnerf_pose_normal_eq_fold: null argument");
-  pn_check_eval(who, points_sensor, n_beams, n_poses, parent_box6, fold_coarse, fold_fine, workspace,
-                workspace_bytes);
-  pn_launch_eval(points_sensor, n_beams, poses12_or_null, n_poses, state_or_null, parent_box6, near, n_samples,
-                 n_importance, fold_coarse, fold_fine, eps, huber_delta, min_sumw, workspace, normal30, depth_or_null,
-                 sumw_or_null, jac6_or_null, (hipStream_t)stream);
-  PCN_LAUNCH_CHECK(who);
-  PCN_API_END_NEG
+  return pn_normal_eq("pcnerf_pose_normal_eq_fold", points_sensor, n_beams, poses12_or_null, n_poses, state_or_null,
+                      {false, nullptr, 1, parent_box6, fold_coarse, fold_fine}, near, n_samples, n_importance, eps,
+                      huber_delta, min_sumw, workspace, workspace_bytes, normal30, depth_or_null, sumw_or_null,
+                      jac6_or_null, (hipStream_t)stream);
+}
+
+extern "C" int pcnerf_pose_normal_eq_map(const float* points_sensor, int64_t n_beams, const double* poses12_or_null,
+                                         int64_t n_poses, const double* state_or_null, const int32_t* block_of_pose,
+                                         int n_blocks, const double* boxes6, float near, int n_samples,
+                                         int n_importance, const double* folds_coarse, const double* folds_fine,
+                                         float eps, double huber_delta, double min_sumw, void* workspace,
+                                         size_t workspace_bytes, double* normal30, float* depth_or_null,
+                                         float* sumw_or_null, float* jac6_or_null, void* stream) {
+  return pn_normal_eq("pcnerf_pose_normal_eq_map", points_sensor, n_beams, poses12_or_null, n_poses, state_or_null,
+                      {true, block_of_pose, n_blocks, boxes6, folds_coarse, folds_fine}, near, n_samples, n_importance,
+                      eps, huber_delta, min_sumw, workspace, workspace_bytes, normal30, depth_or_null, sumw_or_null,
+                      jac6_or_null, (hipStream_t)stream);
 }
 
 extern "C" int pcnerf_lm_init(const double* poses12, int64_t n_poses, double damping, double* state, void* stream) {
@@ -455,35 +539,23 @@ extern "C" int pcnerf_refine_poses_fold(const float* points_sensor, int64_t n_be
                                         int iters, void* workspace, size_t workspace_bytes, double* normal30,
                                         double* state, double* poses12_out, double* eval_costs, uint8_t* accepted,
                                         void* stream) {
-  PCN_API_BEGIN
-  const char* who = "pcnerf_refine_poses_fold";
-  PCN_CHECK(n_poses >= 0 && n_beams >= 0, "pcnerf_refine_poses_fold: negative count");
-  PCN_CHECK(iters >= 0, "pcnerf_refine_poses_fold: iters < 0");
-  fr_check_samples(who, n_samples, n_importance);
-  if (n_poses == 0) return 0;
-  PCN_CHECK(poses12 && normal30 && state && poses12_out, "pcnerf_refine_poses_fold: null argument");
-  PCN_CHECK(iters == 0 || (eval_costs && accepted), "pcnerf_refine_poses_fold: null argument");
-  PCN_CHECK(n_poses < (int64_t)1 << 31 && n_poses * ((int64_t)iters + LM_STATE) < (int64_t)1 << 37,
-            "pcnerf_refine_poses_fold: too many poses for one launch");   // (one thread per state / record word)
-  pn_check_eval(who, points_sensor, n_beams, n_poses, parent_box6, fold_coarse, fold_fine, workspace,
-                workspace_bytes);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_lm_init, dim3(lm_blocks(n_poses * LM_STATE)), dim3(64), 0, s, poses12, n_poses, damping,
-                     state);
-  PCN_HIP(hipMemsetAsync(normal30, 0, (size_t)n_poses * 30 * sizeof(double), s));
-  if (iters > 0)
-    hipLaunchKernelGGL(k_lm_records_init, dim3(lm_blocks(n_poses * iters)), dim3(64), 0, s, n_poses * iters,
-                       eval_costs, accepted);
-  for (int it = 0; it < iters; ++it) {   // stream order is the only synchronisation between evaluations
-    pn_launch_eval(points_sensor, n_beams, nullptr, n_poses, state, parent_box6, near, n_samples, n_importance,
-                   fold_coarse, fold_fine, eps, huber_delta, min_sumw, workspace, normal30, nullptr, nullptr, nullptr,
-                   s);
-    hipLaunchKernelGGL(k_lm_update, dim3(lm_blocks(n_poses)), dim3(64), 0, s, normal30, n_poses, xi_tol, state,
-                       eval_costs, accepted, it, iters);
-  }
-  hipLaunchKernelGGL(k_lm_poses_out, dim3(lm_blocks(n_poses * 12)), dim3(64), 0, s, state, n_poses, poses12_out);
-  PCN_LAUNCH_CHECK(who);
-  PCN_API_END_NEG
+  return lm_refine_poses("pcnerf_refine_poses_fold", points_sensor, n_beams, poses12, n_poses,
+                         {false, nullptr, 1, parent_box6, fold_coarse, fold_fine}, near, n_samples, n_importance, eps,
+                         huber_delta, min_sumw, damping, xi_tol, iters, workspace, workspace_bytes, normal30, state,
+                         poses12_out, eval_costs, accepted, (hipStream_t)stream);
+}
+
+extern "C" int pcnerf_refine_poses_map(const float* points_sensor, int64_t n_beams, const double* poses12,
+                                       int64_t n_poses, const int32_t* block_of_pose, int n_blocks,
+                                       const double* boxes6, float near, int n_samples, int n_importance,
+                                       const double* folds_coarse, const double* folds_fine, float eps,
+                                       double huber_delta, double min_sumw, double damping, double xi_tol, int iters,
+                                       void* workspace, size_t workspace_bytes, double* normal30, double* state,
+                                       double* poses12_out, double* eval_costs, uint8_t* accepted, void* stream) {
+  return lm_refine_poses("pcnerf_refine_poses_map", points_sensor, n_beams, poses12, n_poses,
+                         {true, block_of_pose, n_blocks, boxes6, folds_coarse, folds_fine}, near, n_samples,
+                         n_importance, eps, huber_delta, min_sumw, damping, xi_tol, iters, workspace, workspace_bytes,
+                         normal30, state, poses12_out, eval_costs, accepted, (hipStream_t)stream);
 }
 
 extern "C" int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, double* poses12_out,
