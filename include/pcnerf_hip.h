@@ -115,16 +115,6 @@ int pcnerf_nof_query_train(const float* rays, int64_t n_rays, int ray_stride, co
  * as accurate as mode 0.  The reference's own GPU runs used TF32 matmuls (train_kitti.py:267). */
 int pcnerf_set_train_math(int mode);
 
-/* The default training backward's layer kernel, process-wide; returns the previous one.
- * 4 (default): k_bwd_remat3 -- each hidden layer's weight gradient contracted over the 64 encoding columns,
- * (sum_s g_L (x) (e - ebar)) P'_{L-1}^T, with P'_{L-1} the chunk's float64 layer map (x = h_{L-1} - mean = P' (e - ebar)
- * under identity activations, models.py:72) applied once per chunk; the BatchNorm-backward epilogue and the g stores
- * on the weight-gradient waves.  2: k_bwd_remat2 (round 5: over the 256 rematerialised input columns).  Same
- * gradients within the parity envelope (tests/test_backward_gpu.py).  Every other value is refused: -1, a message in
- * pcnerf_last_error(), nothing changed -- 3, k_bwd_remat3 with the epilogue on the data-gradient waves, was measured
- * slower and is no longer built (HISTORY.md). */
-int pcnerf_set_remat_version(int version);
-
 /* NOF.forward in train mode on an embedded batch of n rows (one BatchNorm chunk; running stats updated). */
 int pcnerf_nof_forward_train(const float* emb, int64_t n, const pcnerf_nof_params* params, float momentum,
                              float eps, void* workspace, size_t workspace_bytes, float* p_out, void* stream);

@@ -1344,11 +1344,6 @@ struct TrainWs {
 // products (k_train_h).  Process-wide; pcnerf_set_train_math.  Mode 1 renders config 2 within 1.9e-5 of a float64
 // evaluation of the same rays (fp32 MFMA: 2.2e-5; the reference itself: 1.1e-4) at 1.9x the speed.
 static int g_train_math = 1;
-// The rematerialised backward's layer kernel (pcnerf_set_remat_version): 4 = k_bwd_remat3 (default: weight gradient
-// over the encoding columns, projected by P'^T per chunk; BatchNorm-backward epilogue on the W waves; layer 1's launch
-// forms dW_0's encoding columns itself), 2 = k_bwd_remat2 (round 5's: over the rematerialised x columns; kept for
-// A/B).  3 was k_bwd_remat3 with the epilogue on the D waves: measured slower, not built (HISTORY.md).
-static int g_remat_ver = 4;
 
 static TrainWs carve(void* base, int64_t chunk) {
   const size_t tiles = (size_t)((chunk + 31) / 32);
@@ -1391,17 +1386,6 @@ extern "C" int pcnerf_set_train_math(int mode) {
   }
   const int prev = pcn::g_train_math;
   pcn::g_train_math = mode;
-  return prev;
-}
-
-extern "C" int pcnerf_set_remat_version(int version) {
-  if (version != 2 && version != 4) {
-    pcn::set_error("pcnerf_set_remat_version: remat_version must be 4 (k_bwd_remat3) or 2 (k_bwd_remat2); 3 "
-                   "(k_bwd_remat3 with the epilogue on the D waves) is no longer built");
-    return -1;
-  }
-  const int prev = pcn::g_remat_ver;
-  pcn::g_remat_ver = version;
   return prev;
 }
 
@@ -3013,7 +2997,7 @@ constexpr size_t FB_LDS = 3 * (size_t)FB_BUF + 7 * 128 * sizeof(float);   // spl
 constexpr size_t FB_LDS_OUT = FB_LDS + (4 * 256 + 8 * 64) * sizeof(float);  // + occ_out / BatchNorm 7 constants,
                                                                             //   dL/dlogit slots
 
-// The rematerialised backward (k_bwd_remat, the default since round 5) moves g between layers PRE-SPLIT, scaled by
+// The rematerialised backward (k_bwd_remat3, the default training backward) moves g between layers PRE-SPLIT, scaled by
 // 2^gexp[L], in the byte layout its consumer's LDS holds it, so it is DMA'd with no conversion: per 32-sample tile
 // [part 2][octet o 32][cell][8 fp16] (32 KiB), cell = sample ^ (12 (o & 1)) holding features 8 o .. 8 o + 7 of that
 // sample (gs_off).  That one layout makes the data gradient's 16-byte B-operand reads (16 samples of one octet per
@@ -3767,380 +3751,15 @@ constexpr size_t G7_LDS = 2 * FB_ENC + 1024 * sizeof(float);
 // (profiles/r05_g7_ab.txt)
 constexpr int G7_BLOCKS = 512;
 
-// The rematerialised layer launch (k_bwd_remat2 below): one layer's backward over a chunk in one pass, as k_bwd_fused
-// (a pair of workgroups per tile, halves of the input features, 8 waves; W_L^T rows in registers; one barrier a
-// tile), with
+// ---- k_bwd_remat3: the rematerialised layer launch -- one layer's backward over a chunk in one pass, laid out as
+// k_bwd_fused (a pair of workgroups per tile, halves of the input features, 8 waves split by role between the two
+// waves of each SIMD: waves 0-3 "D", waves 4-7 "W"; W_L^T rows in registers; one barrier a tile), with
 //   * g_L arriving PRE-SPLIT by LDS-DMA straight into the tile's split buffer (no raw buffer, no conversion: its
-//     producer wrote it at 2^gexp[L]), one tile ahead;
-//   * the layer input x = h_{L-1} - mean made on the matrix pipe from the encoding image (two LDS slots, one tile
-//     deeper) and the half's P'_{L-1} rows (LDS, staged once: 12 MFMAs per wave and tile), split into the x half of
-//     the next tile's buffer between the data- and weight-gradient MFMAs;
-//   * g_{L-1} = ((dy - gm) - x kk) invstd gamma written pre-split at 2^gexp[L-1] from a bound fixed in the prologue:
-//     |g_{L-1,i}| <= (sum_j |W_L[j][i]| max|g_L| + |gm_i| + sqrt(n) sigma_i |kk_i|) invstd_i |gamma_i|.
-// HBM per sample: 1 KiB of g_L, 256 B of encoding in, 1 KiB of g_{L-1} out (2.25 KiB; the store path moved 3).
-constexpr size_t RB_PX = 128 * 256;   // the half's P' rows (128 x 16 f16x8), slot q of row r at q ^ (r & 15)
-constexpr size_t RB_LDS = 2 * (size_t)FB_BUF + 2 * FB_ENC + RB_PX + 8 * 128 * sizeof(float);
-static_assert(RB_LDS <= 160 * 1024, "k_bwd_remat2 LDS");
-// k_bwd_remat2<LAY>: that work split by ROLE between the two waves of each SIMD (waves w and w + 4 share a SIMD): waves 0-3 ("D") the data gradient of 32 input features
-// each (W_L^T rows in registers: 2 row blocks, so every 16-byte g read feeds 6 MFMAs instead of 3) and the BatchNorm
-// backward epilogue with the g_{L-1} stores; waves 4-7 ("W") the rematerialisation of 32 x columns each and the
-// weight gradient of 64 neuron rows each (G's 64 x 128 slice in 128 registers).  Per tile a D wave runs MFMAs then
-// VALU (dgrad, epilogue), a W wave VALU-heavy then MFMAs (remat, wgrad), so each SIMD's two waves are in
-// complementary phases between the tile's barriers; the g / encoding DMAs stay spread over all eight waves.
-template <int LAY>
-__global__ __launch_bounds__(512, 1) void k_bwd_remat2(const char* __restrict__ gin, char* __restrict__ gout,
-                                                        const f16x8* __restrict__ wt,
-                                                        const int* __restrict__ sw, int layer, int64_t n,
-                                                        const float* __restrict__ coefp, const float* __restrict__ bnb,
-                                                        const float* __restrict__ gamma, int* __restrict__ gexp,
-                                                        const float* __restrict__ wcol,
-                                                        const unsigned* __restrict__ gmax_in,
-                                                        unsigned* __restrict__ gmax_out, float* __restrict__ part,
-                                                        FbRed red, const char* __restrict__ enc,
-                                                        const f16x8* __restrict__ px, const float* __restrict__ pxs) {
-  constexpr int C = WgradCfg<LAY>::C, COL = LAY == 2 ? 64 : 0;
-  constexpr int NST = 4;   // a D wave's global stores per tile
-  extern __shared__ __attribute__((aligned(16))) char fb[];
-  char* const enb = fb + 2 * FB_BUF;
-  char* const pxl = enb + 2 * FB_ENC;
-  float* const cst = reinterpret_cast<float*>(pxl + RB_PX);   // [csc | cun | gm | kk | invstd | gamma | xs | bound]
-  const int t = threadIdx.x, lane = t & 63, kg = lane >> 4, lm = lane & 15;
-  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int rw = wv & 3;   // index within the role
-  const int bid = (int)blockIdx.x, hf = (bid >> 3) & 1, pr = ((bid >> 4) << 3) | (bid & 7);
-  const int npair = (int)gridDim.x >> 1;
-  const int nt = (int)((n + 31) / 32);
-  const int nk = pr < nt ? (nt - 1 - pr) / npair + 1 : 0;
-  const float rn = sqrtf((float)n);
-  if (t < 128) {
-    const int c = 128 * hf + t;
-    const float invstd = coefp[256 + c];
-    const float bnd = rn / invstd;   // Samuelson: |h - mean| <= sqrt(n) sigma
-    int e = (bnd > 0.0f && bnd < 3.0e38f) ? 14 - ilogbf(bnd) : 0;
-    e = e < -60 ? -60 : e > 60 ? 60 : e;
-    cst[t] = ldexpf(1.0f, e);
-    cst[128 + t] = ldexpf(1.0f, -e);
-    cst[256 + t] = bnb[c];
-    cst[384 + t] = bnb[256 + c];
-    cst[512 + t] = invstd;
-    cst[640 + t] = gamma[c];
-    cst[768 + t] = ldexpf(pxs[c], e);
-  }
-  unsigned gmx = 0;
-  for (int i = 0; i < GMAX_SLOTS; ++i) gmx = max(gmx, gmax_in[i]);
-  {
-    const int c = t & 255;
-    const float invstd = coefp[256 + c];
-    float ob = ((wcol[c] * __uint_as_float(gmx) + fabsf(bnb[c])) + rn / invstd * fabsf(bnb[256 + c])) * invstd *
-               fabsf(gamma[c]) * 1.01f;
-    ob = wave_max_f(ob);
-    if (lane == 0) cst[896 + wv] = ob;
-  }
-  for (int j = t; j < 128 * 16; j += 512) {
-    const int r = j >> 4, q = j & 15;
-    *reinterpret_cast<f16x8*>(pxl + r * 256 + 16 * (q ^ (r & 15))) = px[(size_t)(128 * hf + r) * 16 + q];
-  }
-  const int eg = gexp[layer];
-  const float gun = ldexpf(1.0f, -eg);
-  __syncthreads();
-  float obm = cst[896];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) obm = fmaxf(obm, cst[896 + i]);
-  const int eo = tile_scale_exp(obm);
-  const float gso = ldexpf(1.0f, eo);
-  if (bid == 0 && t == 0) gexp[layer - 1] = eo;
-  // the epilogue's per-feature constants folded (read by the D waves after the barrier below):
-  //   2^eo g_{L-1} = (dy A - B) - (xh + xm) C,  A = dun invstd gamma 2^eo,  B = gm invstd gamma 2^eo,
-  //   C = 2^-e kk invstd gamma 2^eo   (slots 640 / 256 / 384; cun at 128 stays for the W waves)
-  const float dun = ldexpf(1.0f, -sw[layer]) * gun;
-  if (t < 128) {
-    const float sc = cst[512 + t] * cst[640 + t] * gso;
-    const float cb = cst[256 + t] * sc, cc = cst[128 + t] * cst[384 + t] * sc;
-    cst[640 + t] = dun * sc;
-    cst[256 + t] = cb;
-    cst[384 + t] = cc;
-  }
-  auto dma_g = [&](int k) {
-    const int tl = pr + k * npair;
-    char* const sb = fb + (size_t)(k & 1) * FB_BUF;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-      fb_glds16(gin + (size_t)tl * GS_TILE + (4 * wv + m) * 1024 + 16 * ln, sb + (4 * wv + m) * 1024);
-  };
-  auto dma_enc = [&](int k) {
-    const int tl = pr + k * npair;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    fb_glds16(enc + (size_t)tl * FB_ENC + wv * 1024 + ln * 16, enb + (k & 1) * FB_ENC + wv * 1024);
-  };
-  // W waves: x of tile k, columns 32 rw .. 32 rw + 31 of the half (2 row blocks of P'), slot k & 1 -> buffer k & 1
-  auto remat_x = [&](int k) {
-    const char* eb = enb + (k & 1) * FB_ENC;
-    char* const xb = fb + (size_t)(k & 1) * FB_BUF + 2 * FB_GPART;
-    f32x4 ax[2][2] = {{f32x4{}, f32x4{}}, {f32x4{}, f32x4{}}};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      f16x8 pa[2][2];
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const int r = 32 * rw + 16 * rb + lm, q = (2 * ks + p) * 4 + kg;
-          pa[rb][p] = *reinterpret_cast<const f16x8*>(pxl + r * 256 + 16 * (q ^ (r & 15)));
-        }
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        const int o = fb_eoff(16 * sb + lm, 4 * ks + kg);
-        const f16x8 bh = *reinterpret_cast<const f16x8*>(eb + o);
-        const f16x8 bm = *reinterpret_cast<const f16x8*>(eb + FB_ENC / 2 + o);
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bh, ax[rb][sb], 0, 0, 0);
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][0], bm, ax[rb][sb], 0, 0, 0);
-          ax[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa[rb][1], bh, ax[rb][sb], 0, 0, 0);
-        }
-      }
-    }
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-      const int il = 32 * rw + 16 * rb + 4 * kg;
-      const f32x4 xs = *reinterpret_cast<const f32x4*>(cst + 768 + il);
-#pragma unroll
-      for (int sb = 0; sb < 2; ++sb) {
-        f32x4 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = ax[rb][sb][q] * xs[q];
-        s16x4 p0, p1;
-        split2_x4(v, p0, p1);
-        const int o = fb_off<FB_XP>(16 * sb + lm, il);
-        *reinterpret_cast<s16x4*>(xb + o) = p0;
-        *reinterpret_cast<s16x4*>(xb + FB_XPART + o) = p1;
-      }
-    }
-  };
-  if (nk > 0) {
-    dma_g(0);
-    dma_enc(0);
-    if (nk > 1) dma_enc(1);
-    __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
-    __builtin_amdgcn_s_barrier();
-    if (wv >= 4) remat_x(0);
-  }
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  __builtin_amdgcn_s_barrier();
-  if (wv < 4) {
-    // ---- D: data gradient of input features 128 hf + 32 rw + 16 rb + lm, epilogue, g_{L-1} stores
-    const float gui = ldexpf(1.0f, -eo);
-    f16x8 wr[8][2][2];
-    {
-      const f16x8* __restrict__ w8 = wt + lane;
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int p = 0; p < 2; ++p) wr[ks][rb][p] = w8[((ks * 16 + 8 * hf + 2 * rw + rb) * 2 + p) * 64];
-    }
-    // the W^T rows used once before the loop: otherwise the waitcnt pass sees their loads pending at the loop header
-    // and waits vmcnt(0) at every tile's first MFMA -- i.e. for the DMAs the tile has just issued
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-      asm volatile("" ::"v"(wr[ks][0][0]), "v"(wr[ks][0][1]), "v"(wr[ks][1][0]), "v"(wr[ks][1][1]));
-    float gmo = 0.0f;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 pcell[2][2] = {{u32x4{}, u32x4{}}, {u32x4{}, u32x4{}}};
-    // a cell's g_{L-1} store (tile tq): the split pair as one 16-byte cell
-    auto store_cell = [&](int rb, int sb, int tq, const u32x4& cell) {
-      const int i = 128 * hf + 32 * rw + 16 * rb + 4 * kg, sm = 16 * sb + lm;
-      char* gt = gout + (size_t)tq * GS_TILE + (kg & 1) * FB_GPART + gs_off(sm, i >> 3);
-#if PCN_RB_NOSTORE
-      if (cell[0] == 12345u && cell[3] == 4321u)
-#endif
-      __builtin_nontemporal_store(cell, reinterpret_cast<u32x4*>(gt));   // streaming: keep L2 for the g / encoding tiles the other half re-reads
-    };
-    // tile k's g_{L-1} cells are stored during tile k + 1's data-gradient MFMAs, one cell after every second k-step
-    // (pinned there by scheduling barriers: left to the scheduler they sink to the phase's end), so the D waves'
-    // stores do not meet every CU's at the epilogue: -1.6 % per launch (profiles/r05_variants_remat2_defer.txt)
-    // (tile 0: zero cells to tile 0's own slots, rewritten by this wave's later stores of its real cells -- same
-    // addresses, program order; they also keep NST stores behind every tile's DMAs for the vmcnt(NST) below)
-    for (int k = 0; k < nk; ++k) {
-      const int tl = pr + k * npair;
-      const int ptl = k > 0 ? tl - npair : tl;
-#if !PCN_RB_NODMA
-      if (k + 1 < nk) dma_g(k + 1);
-      if (k + 2 < nk) dma_enc(k + 2);
-#endif
-      const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-      const char* xb = sp + 2 * FB_GPART;
-      f32x4 ad[2][2] = {{f32x4{}, f32x4{}}, {f32x4{}, f32x4{}}};
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-          const int o = gs_off(16 * sb + lm, 4 * ks + kg);
-          const f16x8 bh = *reinterpret_cast<const f16x8*>(sp + o);
-          const f16x8 bm = *reinterpret_cast<const f16x8*>(sp + FB_GPART + o);
-#pragma unroll
-          for (int rb = 0; rb < 2; ++rb) {
-#if PCN_RB_NODG
-            ad[rb][sb] += __builtin_bit_cast(f32x4, bh) + __builtin_bit_cast(f32x4, bm);
-#else
-            ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][0], bh, ad[rb][sb], 0, 0, 0);
-            ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][0], bm, ad[rb][sb], 0, 0, 0);
-            ad[rb][sb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wr[ks][rb][1], bh, ad[rb][sb], 0, 0, 0);
-#endif
-          }
-          if ((ks & 1) && sb == 1) {
-            store_cell((ks >> 2) & 1, (ks >> 1) & 1, ptl, pcell[(ks >> 2) & 1][(ks >> 1) & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) {
-        const int il = 32 * rw + 16 * rb + 4 * kg;
-        const f32x4 cA = *reinterpret_cast<const f32x4*>(cst + 640 + il);
-        const f32x4 cB = *reinterpret_cast<const f32x4*>(cst + 256 + il);
-        const f32x4 cC = *reinterpret_cast<const f32x4*>(cst + 384 + il);
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-          const int sm = 16 * sb + lm;
-          const bool valid = (int64_t)tl * 32 + sm < n;
-          const int o = fb_off<FB_XP>(sm, il);
-          const f16x4 xh = *reinterpret_cast<const f16x4*>(xb + o);
-          const f16x4 xm = *reinterpret_cast<const f16x4*>(xb + FB_XPART + o);
-          f32x4 vs;   // 2^eo g_{L-1}
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float xs = (float)xh[q] + (float)xm[q];   // exact: the split's two parts
-            vs[q] = valid ? fmaf(-xs, cC[q], fmaf(ad[rb][sb][q], cA[q], -cB[q])) : 0.0f;
-            gmo = fmaxf(gmo, fabsf(vs[q]));
-          }
-          s16x4 p0, p1;
-          split2_x4(vs, p0, p1);
-          // one 16-byte cell per lane: the lanes of 16-lane rows 2r / 2r+1 (kg even / odd: features i .. i+3 and
-          // i+4 .. i+7 of one octet) swap halves (v_permlane16_swap: the odd row's first operand <-> the even
-          // row's second), so the even row stores the octet's hi part and the odd row its mid part
-          const fb_i32x2 hv = __builtin_bit_cast(fb_i32x2, p0), mv = __builtin_bit_cast(fb_i32x2, p1);
-          const auto s0 = __builtin_amdgcn_permlane16_swap(hv[0], mv[0], false, false);
-          const auto s1 = __builtin_amdgcn_permlane16_swap(hv[1], mv[1], false, false);
-          pcell[rb][sb] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-        }
-      }
-#if !PCN_RB_NOWAIT
-      __builtin_amdgcn_s_waitcnt(fb_vmcnt(NST));   // this wave's DMAs (its stores may fly)
-#endif
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-    }
-    if (nk > 0) {   // the last tile's cells
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) store_cell(rb, sb, pr + (nk - 1) * npair, pcell[rb][sb]);
-    }
-    gmo = wave_max_f(gmo) * gui;
-    if (lane == 0) atomicMax(gmax_out + ((bid * 4 + rw) & (GMAX_SLOTS - 1)), __float_as_uint(gmo));
-  } else {
-    // ---- W: x of tile k + 1, weight gradient rows j = 64 rw + 16 jb + lm (4 blocks) x the half's 128 columns
-    f32x4 aw[4][8];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-      for (int ib = 0; ib < 8; ++ib) aw[jb][ib] = f32x4{};
-    const int trq = lm >> 2, trp = lm & 3;
-    for (int k = 0; k < nk; ++k) {
-#if !PCN_RB_NODMA
-      if (k + 1 < nk) dma_g(k + 1);
-      if (k + 2 < nk) dma_enc(k + 2);
-#endif
-#if !PCN_RB_NORM
-      if (k + 1 < nk) remat_x(k + 1);
-#endif
-      const char* const sp = fb + (size_t)(k & 1) * FB_BUF;
-      auto read8 = [&](unsigned a0, unsigned a1, auto partc) {
-        constexpr int Q = decltype(partc)::value;
-        const s16x4 h0 = fb_tr<0>(a0), h1 = fb_tr<0>(a1), m0 = fb_tr<Q>(a0), m1 = fb_tr<Q>(a1);
-        return std::array<s16x4, 4>{h0, h1, m0, m1};
-      };
-      auto join = [](const s16x4& a, const s16x4& b) {
-        return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-      };
-      using QG = std::integral_constant<int, FB_GPART>;
-      using QX = std::integral_constant<int, FB_XPART>;
-      const unsigned ga = fb_lds_addr(sp), xa = fb_lds_addr(sp + 2 * FB_GPART);
-      const int tr0 = 8 * kg + trq, tr1 = tr0 + 4;
-      auto xrd = [&](int ib) {
-        const int col = 16 * ib + 4 * trp;
-        return read8(xa + fb_off<FB_XP>(tr0, col), xa + fb_off<FB_XP>(tr1, col), QX{});
-      };
-      std::array<s16x4, 4> ra[4], rbx[2];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const int col = 64 * rw + 16 * jb + 4 * trp;
-        ra[jb] = read8(ga + gs_off(tr0, col >> 3) + 2 * (col & 7), ga + gs_off(tr1, col >> 3) + 2 * (col & 7), QG{});
-      }
-      rbx[0] = xrd(0);
-      fb_lgkm<4>(ra);
-      f16x8 A[4][2];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        A[jb][0] = join(ra[jb][0], ra[jb][1]);
-        A[jb][1] = join(ra[jb][2], ra[jb][3]);
-      }
-#pragma unroll
-      for (int ib = 0; ib < 8; ++ib) {
-        std::array<s16x4, 4> cur[1] = {rbx[ib & 1]};
-        if (ib + 1 < 8) {
-          rbx[(ib + 1) & 1] = xrd(ib + 1);
-          fb_lgkm<4>(cur);
-        } else {
-          fb_lgkm<0>(cur);
-        }
-        rbx[ib & 1] = cur[0];
-        const f16x8 B0 = join(rbx[ib & 1][0], rbx[ib & 1][1]), B1 = join(rbx[ib & 1][2], rbx[ib & 1][3]);
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-#if PCN_RB_NOWG
-          aw[jb][ib] += __builtin_bit_cast(f32x4, B0) + __builtin_bit_cast(f32x4, A[jb][1]);
-#else
-          aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[jb][0], B0, aw[jb][ib], 0, 0, 0);
-          aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[jb][0], B1, aw[jb][ib], 0, 0, 0);
-          aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[jb][1], B0, aw[jb][ib], 0, 0, 0);
-#endif
-        }
-      }
-#if !PCN_RB_NOWAIT
-      __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
-#endif
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-    }
-    float* pb = part + (size_t)pr * WgradCfg<LAY>::PART;
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib) {
-      const float cu = cst[128 + 16 * ib + lm] * gun;
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          pb[(size_t)(64 * rw + 16 * jb + 4 * kg + r) * C + COL + 128 * hf + 16 * ib + lm] = aw[jb][ib][r] * cu;
-    }
-    // sum_s g_L (the Linear bias gradient, and the beta_{L-1} term of dW_L in the reduction): exactly zero -- BatchNorm
-    // L's backward leaves every neuron's g with zero chunk mean (models.py:183-203: Linear -> BatchNorm); the
-    // reference's autograd carries rounding noise there, the fold path an exact zero like this one
-    if (hf == 0 && kg == 0) {
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) pb[(size_t)256 * C + 64 * rw + 16 * jb + lm] = 0.0f;
-    }
-  }
-  __syncthreads();
-  if (red.mode != 0) fb_reduce_row(red, reinterpret_cast<double*>(fb), t);
-}
-
-// ---- k_bwd_remat3: the rematerialised layer launch with the weight gradient taken over the ENCODING columns
-// (VERDICT r5 item 2).  Inside a chunk every layer input is x = h_{L-1} - mean_{L-1} = P'_{L-1} d (d = e - ebar, the
+//     producer wrote it at 2^gexp[L]), one tile ahead; the encoding image by LDS-DMA two tiles ahead;
+//   * g_{L-1} written pre-split at 2^gexp[L-1] from a bound fixed in the prologue:
+//     |g_{L-1,i}| <= (sum_j |W_L[j][i]| max|g_L| + |gm_i| + sqrt(n) sigma_i |kk_i|) invstd_i |gamma_i|;
+//   * HBM per sample: 1 KiB of g_L, 256 B of encoding in, 1 KiB of g_{L-1} out (2.25 KiB; the store path moved 3);
+// and with the weight gradient taken over the ENCODING columns.  Inside a chunk every layer input is x = h_{L-1} - mean_{L-1} = P'_{L-1} d (d = e - ebar, the
 // identity-activation premise the remat already rests on) and sum_s g_L = 0 (BatchNorm L's backward), so
 //   G_L = sum_s g_L (x) x = (sum_s g_L (x) d) P'_{L-1}^T :
 // the tile loop contracts g_L with the 64 encoding columns (24 MFMAs per W wave and tile instead of 96 over the 256
@@ -4684,125 +4303,6 @@ __global__ __launch_bounds__(256) void k_gd_proj(GdProj g) {
   }
 }
 
-// k_wgrad_enc: the encoding columns of dW_0 and of the skip layer's dW_4, G = sum_s g (x) d, from the PRE-SPLIT g_0 and
-// g_4 images (k_bwd_remat2's output layout, gs_off) and the chunk's encoding image (k_remat_enc: d = e - ebar, fb_eoff),
-// DMA'd straight into LDS -- no sincos, no conversion.  d in place of e: sum_s g_L = 0 exactly (BatchNorm follows
-// both Linears), so sum g (x) e = sum g (x) d; the layer-0 bias gradient sum_s g_0 is that exact 0.  The two sources
-// split between the workgroups of a pair (blocks b and b + 8: the same XCD, so the encoding tile's second read is an
-// L2 hit): 40 KiB per tile (one g image + the encoding), a ring of three slots, DMA two tiles ahead (-5 % against
-// one workgroup taking both sources at 72 KiB per tile, double-buffered; four slots: no change;
-// profiles/r05_wgrad_enc_ab.txt).  8 waves x 32 rows (2 x 16) x the 64 columns in 32 registers; per tile and wave
-// 24 transposed reads (ds_read_b64_tr_b16) and 24 v_mfma_f32_16x16x32_f16 (hi.hi + hi.mid + mid.hi).  Partials in
-// k_wgrad<1>'s layout, one set per pair and source, unscaled (2^-gexp of the image, 2^-s of the column), summed by
-// k_fb_reduce_tail.  HBM per sample: 2 KiB of g + 256 B of encoding.
-constexpr int WE_SLOTS = 3, WE_AHEAD = WE_SLOTS - 1;
-constexpr size_t WE_BUF = (size_t)GS_TILE + FB_ENC;
-constexpr size_t WE_LDS = WE_SLOTS * WE_BUF;
-static_assert(WE_LDS <= 160 * 1024, "k_wgrad_enc LDS");
-__global__ __launch_bounds__(512, 1) void k_wgrad_enc(const char* __restrict__ g0, const char* __restrict__ g4,
-                                                       const char* __restrict__ enc, int64_t n,
-                                                       const int* __restrict__ gexp, const unsigned* __restrict__ pbound,
-                                                       float* __restrict__ part0, float* __restrict__ part4) {
-  extern __shared__ __attribute__((aligned(16))) char wel[];
-  const int t = threadIdx.x, lane = t & 63, kg = lane >> 4, lm = lane & 15;
-  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  // g4 null (the default, k_bwd_remat3 takes the skip layer's encoding columns): every workgroup its own tiles of
-  // g_0 and its own partial set; otherwise the pairs split by source
-  const bool one = g4 == nullptr;
-  const int bid = (int)blockIdx.x, src = one ? 0 : (bid >> 3) & 1;
-  const int pr = one ? bid : ((bid >> 4) << 3) | (bid & 7);
-  const int npair = one ? (int)gridDim.x : (int)gridDim.x >> 1;
-  const int nt = (int)((n + 31) / 32);
-  const int nk = pr < nt ? (nt - 1 - pr) / npair + 1 : 0;
-  const char* const gsrc = src == 0 ? g0 : g4;
-  // one tile: 40 pieces of 1 KiB (g 0..31, encoding 32..39), 5 per wave, into slot k % 3
-  auto dma = [&](int k) {
-    const size_t tl = (size_t)(pr + k * npair);
-    char* const b = wel + (size_t)(k % WE_SLOTS) * WE_BUF;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int p = 5 * wv + i;
-      const char* a = p < 32 ? gsrc + tl * GS_TILE + p * 1024 : enc + tl * FB_ENC + (p - 32) * 1024;
-      fb_glds16(a + 16 * ln, b + p * 1024);
-    }
-  };
-  auto eoff = [](int r, int c) { return r * 128 + 16 * ((c >> 3) ^ ((r >> 1) & 7)) + 2 * (c & 7); };
-  auto join = [](const s16x4& a, const s16x4& b) {
-    return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
-  f32x4 aw[2][4];
-#pragma unroll
-  for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib) aw[jb][ib] = f32x4{};
-  const int trq = lm >> 2, trp = lm & 3, tr0 = 8 * kg + trq, tr1 = tr0 + 4;
-  // this wave's DMAs done but for the last m tiles' (5 each)
-  auto wait_ahead = [](int m) {
-    if (m >= 2) __builtin_amdgcn_s_waitcnt(fb_vmcnt(10));
-    else if (m == 1) __builtin_amdgcn_s_waitcnt(fb_vmcnt(5));
-    else __builtin_amdgcn_s_waitcnt(fb_vmcnt(0));
-  };
-  static_assert(WE_AHEAD <= 3, "wait_ahead");
-#pragma unroll
-  for (int j = 0; j < WE_AHEAD; ++j)
-    if (j < nk) dma(j);
-  wait_ahead(min(WE_AHEAD - 1, nk - 1));
-  __builtin_amdgcn_s_barrier();
-  for (int k = 0; k < nk; ++k) {
-    if (k + WE_AHEAD < nk) dma(k + WE_AHEAD);
-    const char* const b = wel + (size_t)(k % WE_SLOTS) * WE_BUF;
-    const unsigned ga = fb_lds_addr(b), ea = fb_lds_addr(b + GS_TILE);
-    std::array<s16x4, 4> ra[2], rx[4];
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb) {
-      const int col = 32 * wv + 16 * jb + 4 * trp;
-      const unsigned a0 = ga + gs_off(tr0, col >> 3) + 2 * (col & 7), a1 = ga + gs_off(tr1, col >> 3) + 2 * (col & 7);
-      ra[jb] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_GPART>(a0), fb_tr<FB_GPART>(a1)};
-    }
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib) {
-      const int c = 16 * ib + 4 * trp;
-      const unsigned a0 = ea + eoff(tr0, c), a1 = ea + eoff(tr1, c);
-      rx[ib] = std::array<s16x4, 4>{fb_tr<0>(a0), fb_tr<0>(a1), fb_tr<FB_ENC / 2>(a0), fb_tr<FB_ENC / 2>(a1)};
-    }
-    fb_lgkm<0>(ra);
-    fb_lgkm<0>(rx);
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib) {
-      const f16x8 B0 = join(rx[ib][0], rx[ib][1]), B1 = join(rx[ib][2], rx[ib][3]);
-#pragma unroll
-      for (int jb = 0; jb < 2; ++jb) {
-        const f16x8 A0 = join(ra[jb][0], ra[jb][1]), A1 = join(ra[jb][2], ra[jb][3]);
-        aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, aw[jb][ib], 0, 0, 0);
-        aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B1, aw[jb][ib], 0, 0, 0);
-        aw[jb][ib] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B0, aw[jb][ib], 0, 0, 0);
-      }
-    }
-    wait_ahead(max(0, min(k + WE_AHEAD, nk - 1) - (k + 1)));   // tile k + 1's DMA landed (later tiles' may fly)
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
-  }
-  constexpr int C = WgradCfg<1>::C;
-  float* const pb = (src == 0 ? part0 : part4) + (size_t)pr * WgradCfg<1>::PART;
-  const float gu = ldexpf(1.0f, -gexp[src == 0 ? 0 : 4]);
-  const int sxyz = remat_sx(0, __uint_as_float(*pbound));
-#pragma unroll
-  for (int ib = 0; ib < 4; ++ib) {
-    const int col = 16 * ib + lm;
-    const float cu = ldexpf(gu, -(col < 3 ? sxyz : 13));
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pb[(size_t)(32 * wv + 16 * jb + 4 * kg + r) * C + col] = aw[jb][ib][r] * cu;
-  }
-  if (kg == 0) {
-#pragma unroll
-    for (int jb = 0; jb < 2; ++jb) pb[(size_t)256 * C + 32 * wv + 16 * jb + lm] = 0.0f;
-  }
-}
-
 struct GradTable {
   float* dst[34];
   int64_t off[34];
@@ -5064,20 +4564,75 @@ static void fused_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs&
                      ws.gacc + G.w[4], FB_PAIRS, (int)we);
 }
 
-// k_bwd_remat3's layers of one chunk (after k_g7): layers 7..1 (each launch's tail sums the previous layer's G_d
-// partials into ws.gd; layer 1's also forms dW_0's encoding columns), k_gd_tail (layer 1's G_d, dW_0), k_gd_proj
-// (every layer's dW_L += alpha (G_d P'^T), and the skip layer's encoding columns)
-template <class PR, class PS>
-static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
-                          int64_t ci, int64_t n, hipStream_t s, char* encimg, const PR& prow, const PS& psrow,
-                          char* const (&S)[2], char* S2, float* const (&pset)[2]) {
+// One chunk through the rematerialised backward (no activation store), in launch order:
+//   k_out_gabs   max |dL/dlogit|
+//   k_fb_prep    every constant of the chunk's layers, on the fold's statistics
+//   k_remat_enc  the chunk's encoding image
+//   k_g7         g_7, pre-split, into S[0]
+//   k_bwd_remat3 layers 7..1, g ping-ponging between S[0] and S[1]; each launch's tail sums the previous layer's G_d
+//                partials into ws.gd; layer 1's also forms dW_0's encoding columns and keeps g_0 in LDS
+//   k_gd_tail    layer 1's G_d and dW_0, db_0
+//   k_gd_proj    every layer's dW_L += alpha (G_d P'^T), and the skip layer's encoding columns
+static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
+                        const f16x8* pimg, const float* pscl, int64_t ci, int64_t c0, int64_t n, const float* rays,
+                        int ray_stride, const float* z, int n_samples, float eps, const float* grad, hipStream_t s,
+                        const float* pts) {
+  static std::atomic<uint64_t> attr{0};
+  if (pcn_attr_needed(attr)) {
+    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, false, 4>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3_LDS));
+    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, true, 4>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3L_LDS));
+    PCN_HIP(hipFuncSetAttribute((const void*)k_g7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G7_LDS));
+    pcn_attr_done(attr);
+  }
   const double dn = (double)n;
+  const int64_t ntiles = (n + 31) / 32;
+  const unsigned eg = (unsigned)((ntiles + 3) / 4 < 1024 ? (ntiles + 3) / 4 : 1024);
+  {
+    // k_out_gabs reads 4 B per sample; k_fb_prep's traffic is per chunk (a few KB)
+    ProfScope ps(s, PT_BWD_MISC, 0.0, 4.0 * dn);
+    unsigned* gvmax = reinterpret_cast<unsigned*>(ws.ostat);
+    hipLaunchKernelGGL(k_out_gabs, dim3(eg < 256 ? eg : 256), dim3(256), 0, s, grad + c0, n, gvmax);
+    FbPrepOut po;
+    for (int L = 0; L < 8; ++L) po.g[L] = G.g[L];
+    po.d_beta7 = ws.gacc + G.be[7];
+    po.d_wout = ws.gacc + G.wo;
+    po.d_bout = ws.gacc + G.bo;
+    hipLaunchKernelGGL(k_fb_prep, dim3(8), dim3(256), 0, s, P, (const double*)nullptr, n, eps, ws.coef, FB, ci,
+                       ws.bnb, ws.gacc, po, FB.oacc + ci * 257, gvmax, ws.ocst, ws.gmax);
+  }
+  char* const encimg = reinterpret_cast<char*>(ws.enc);
+  const int64_t C = FB.C;
+  auto prow = [&](int L) { return pimg + ((size_t)L * C + ci) * 256 * 16; };
+  auto psrow = [&](int L) { return pscl + ((size_t)L * C + ci) * 256; };
+  char* const S[2] = {reinterpret_cast<char*>(ws.h[0]), reinterpret_cast<char*>(ws.h[1])};
+  {
+    // the encoding (30 sincosf per sample): 4 B of z in, 256 B of image out per sample
+    ProfScope ps(s, PT_BWD_REMAT, 0.0, (4.0 + 256.0) * dn);
+    const dim3 rg((unsigned)((ntiles + RE_TILES - 1) / RE_TILES));
+    if (pts)
+      hipLaunchKernelGGL(k_remat_enc<true>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
+                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
+    else
+      hipLaunchKernelGGL(k_remat_enc<false>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
+                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
+  }
+  {
+    // g_7: 2 x 256 x 64 fp32-FLOP per sample (h_7 - mean_7); 256 B of image + 4 B in, 1 KiB out
+    ProfScope ps(s, PT_BWD_REMAT, 2.0 * 256.0 * 64.0 * dn, (260.0 + 1024.0) * dn);
+    hipLaunchKernelGGL(k_g7, dim3((unsigned)std::min<int64_t>(ntiles, G7_BLOCKS)), dim3(512), G7_LDS, s, encimg,
+                       grad + c0, n, prow(7), psrow(7), (const float*)ws.ocst, ws.gmax + 7 * GMAX_SLOTS, ws.gexp,
+                       ws.gm7, S[0]);
+  }
   const unsigned fbg = (unsigned)(2 * FB_PAIRS);
+  // two partial sets, by layer parity: layer L's launch writes set L & 1 and sums layer L + 1's set in its tail
+  float* const pset[2] = {ws.part, ws.part + (size_t)FB_PAIRS * WgradCfg<2>::PART};
   float* const part_e0 = ws.part + 2 * (size_t)FB_PAIRS * WgradCfg<2>::PART;
   for (int L = 7; L >= 1; --L) {
     const float* coefp = ws.coef + 1024 * (L - 1);
-    const char* gin = L == 4 ? S2 : S[(7 - L) & 1];
-    char* gout = L == 5 ? S2 : S[(8 - L) & 1];
+    const char* gin = S[(7 - L) & 1];
+    char* gout = S[(8 - L) & 1];
     const unsigned* gmin = L == 7 ? ws.gm7 : ws.gmax + L * GMAX_SLOTS;
     const float* rpart = L < 7 ? pset[(L + 1) & 1] : nullptr;
     double* rgd = ws.gd + (size_t)(L + 1) * GD_LAYER;
@@ -5112,112 +4667,6 @@ static void remat3_layers(const NofParamsDev& P, const GaccLayout& G, const BwdW
   gp.C = FB.C;
   gp.ci = ci;
   hipLaunchKernelGGL(k_gd_proj, dim3(16, 7), dim3(256), 0, s, gp);
-}
-
-// One chunk through the rematerialised backward (no activation store): max |dL/dlogit|, k_fb_prep on the fold's
-// statistics, the chunk's encoding image, g_7 (k_g7), then the layers: remat3_layers (the default), or under remat
-// version 2 layers 7..1 each in ONE k_bwd_remat2 launch, the encoding columns of layers 0 and 4 (k_wgrad_enc on the
-// pre-split g_0 and g_4 and the encoding image) and the last partial sums.
-// g buffers, all pre-split: S0 / S1 alternate (g_7, g_5, g_3, g_1 in S0; g_6, g_2, g_0 in S1), g_4 in S2 (kept to
-// the end for k_wgrad_enc; the default keeps g_0 in LDS).
-static void remat_chunk(const NofParamsDev& P, const GaccLayout& G, const BwdWs& ws, const FoldBnBwd& FB,
-                        const f16x8* pimg, const float* pscl, int64_t ci, int64_t c0, int64_t n, const float* rays,
-                        int ray_stride, const float* z, int n_samples, float eps, const float* grad, hipStream_t s,
-                        const float* pts) {
-  static std::atomic<uint64_t> attr{0};
-  if (pcn_attr_needed(attr)) {
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat2<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)RB_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat2<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)RB_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, false, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_bwd_remat3<true, true, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)R3L_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_g7, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G7_LDS));
-    PCN_HIP(hipFuncSetAttribute((const void*)k_wgrad_enc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WE_LDS));
-    pcn_attr_done(attr);
-  }
-  const double dn = (double)n;
-  const int64_t ntiles = (n + 31) / 32;
-  const unsigned eg = (unsigned)((ntiles + 3) / 4 < 1024 ? (ntiles + 3) / 4 : 1024);
-  {
-    // k_out_gabs reads 4 B per sample; k_fb_prep's traffic is per chunk (a few KB)
-    ProfScope ps(s, PT_BWD_MISC, 0.0, 4.0 * dn);
-    unsigned* gvmax = reinterpret_cast<unsigned*>(ws.ostat);
-    hipLaunchKernelGGL(k_out_gabs, dim3(eg < 256 ? eg : 256), dim3(256), 0, s, grad + c0, n, gvmax);
-    FbPrepOut po;
-    for (int L = 0; L < 8; ++L) po.g[L] = G.g[L];
-    po.d_beta7 = ws.gacc + G.be[7];
-    po.d_wout = ws.gacc + G.wo;
-    po.d_bout = ws.gacc + G.bo;
-    hipLaunchKernelGGL(k_fb_prep, dim3(8), dim3(256), 0, s, P, (const double*)nullptr, n, eps, ws.coef, FB, ci,
-                       ws.bnb, ws.gacc, po, FB.oacc + ci * 257, gvmax, ws.ocst, ws.gmax);
-  }
-  char* const encimg = reinterpret_cast<char*>(ws.enc);
-  const int64_t C = FB.C;
-  auto prow = [&](int L) { return pimg + ((size_t)L * C + ci) * 256 * 16; };
-  auto psrow = [&](int L) { return pscl + ((size_t)L * C + ci) * 256; };
-  char* const S[2] = {reinterpret_cast<char*>(ws.h[0]), reinterpret_cast<char*>(ws.h[1])};
-  char* const S2 = reinterpret_cast<char*>(ws.h[2]);
-  {
-    // the encoding (30 sincosf per sample): 4 B of z in, 256 B of image out per sample
-    ProfScope ps(s, PT_BWD_REMAT, 0.0, (4.0 + 256.0) * dn);
-    const dim3 rg((unsigned)((ntiles + RE_TILES - 1) / RE_TILES));
-    if (pts)
-      hipLaunchKernelGGL(k_remat_enc<true>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
-                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
-    else
-      hipLaunchKernelGGL(k_remat_enc<false>, rg, dim3(32 * RE_TILES), 0, s, rays, ray_stride, z, n_samples, c0, n,
-                         FB.eb + ci * 64, ws.pbound, encimg, ws.gm7, pts);
-  }
-  {
-    // g_7: 2 x 256 x 64 fp32-FLOP per sample (h_7 - mean_7); 256 B of image + 4 B in, 1 KiB out
-    ProfScope ps(s, PT_BWD_REMAT, 2.0 * 256.0 * 64.0 * dn, (260.0 + 1024.0) * dn);
-    hipLaunchKernelGGL(k_g7, dim3((unsigned)std::min<int64_t>(ntiles, G7_BLOCKS)), dim3(512), G7_LDS, s, encimg,
-                       grad + c0, n, prow(7), psrow(7), (const float*)ws.ocst, ws.gmax + 7 * GMAX_SLOTS, ws.gexp,
-                       ws.gm7, S[0]);
-  }
-  const unsigned fbg = (unsigned)(2 * FB_PAIRS);
-  float* const pset[2] = {ws.part, ws.part + (size_t)FB_PAIRS * WgradCfg<2>::PART};
-  if (g_remat_ver == 4) {
-    remat3_layers(P, G, ws, FB, ci, n, s, encimg, prow, psrow, S, S2, pset);
-    return;
-  }
-  for (int L = 7; L >= 1; --L) {
-    const float* coefp = ws.coef + 1024 * (L - 1);
-    FbRed red{nullptr, nullptr, nullptr, nullptr, 0};
-    if (L < 7)
-      red = FbRed{pset[(L + 1) & 1], ws.coef + 1024 * L, ws.gacc + G.w[L + 1], ws.gacc + G.b[L + 1], L + 1 == 4 ? 2 : 1};
-    const char* gin = L == 4 ? S2 : S[(7 - L) & 1];
-    char* gout = L == 5 ? S2 : S[(8 - L) & 1];
-    const unsigned* gmin = L == 7 ? ws.gm7 : ws.gmax + L * GMAX_SLOTS;
-    // algorithmic work: data and weight gradient (2 x 2 x 256 x 256) + the input's rematerialisation (2 x 256 x 64);
-    // bytes: g_L in (1 KiB), the encoding image (256 B), g_{L-1} out (1 KiB)
-    ProfScope ps(s, PT_BWD_FUSED, (2.0 * 2.0 * 256.0 * 256.0 + 2.0 * 256.0 * 64.0) * dn, (1024.0 + 256.0 + 1024.0) * dn);
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(fbg), dim3(512), RB_LDS, s, gin, gout, ws.wth16 + (size_t)(L - 1) * HW_H,
-                         (const int*)ws.sw, L, n, coefp, (const float*)(ws.bnb + 512 * (L - 1)), P.bn_w[L - 1],
-                         ws.gexp, (const float*)(ws.wcol + (L - 1) * 256), gmin, ws.gmax + (L - 1) * GMAX_SLOTS,
-                         pset[L & 1], red, (const char*)encimg, prow(L - 1), psrow(L - 1));
-    };
-    if (L == 4) launch(k_bwd_remat2<2>);
-    else launch(k_bwd_remat2<0>);
-  }
-  const int ne = (int)std::min<int64_t>(ntiles, FB_PAIRS);   // encoding-column partial sets (one per pair)
-  float* const part_e0 = ws.part + 2 * (size_t)FB_PAIRS * WgradCfg<2>::PART;
-  float* const part_e4 = part_e0 + (size_t)WG_BLOCKS * WgradCfg<1>::PART;
-  {
-    // 2 x 2 x 256 x 64 fp32-FLOP per sample; 2 KiB of g + 256 B of encoding in
-    ProfScope ps(s, PT_BWD_WGRAD_H, 2.0 * 2.0 * 256.0 * 64 * dn, (2048.0 + 256.0) * dn);
-    hipLaunchKernelGGL(k_wgrad_enc, dim3(2 * FB_PAIRS), dim3(512), WE_LDS, s, (const char*)S[1], (const char*)S2,
-                       (const char*)encimg, n, (const int*)ws.gexp, (const unsigned*)ws.pbound, part_e0, part_e4);
-  }
-  // the partial sums read (k_fb_reduce_tail): layer 1's pair partials and the two encoding-column sets
-  ProfScope ps(s, PT_BWD_MISC, 0.0, (double)FB_PAIRS * WgradCfg<0>::PART * 4.0 + 2.0 * ne * WgradCfg<1>::PART * 4.0);
-  hipLaunchKernelGGL(k_fb_reduce_tail, dim3(256, 3), dim3(1024), 0, s, pset[1], (const float*)ws.coef,
-                     ws.gacc + G.w[1], ws.gacc + G.b[1], part_e0, ws.gacc + G.w[0], ws.gacc + G.b[0], part_e4,
-                     ws.gacc + G.w[4], FB_PAIRS, ne);
 }
 
 static void emit_grads(const GaccLayout& G, const BwdWs& ws, const pcnerf_nof_grads* grads, hipStream_t s) {

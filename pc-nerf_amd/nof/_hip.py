@@ -43,7 +43,6 @@ _SIGS = {
     "pcnerf_nof_query_eval": (c_int, [vp, i64, c_int, vp, c_int, vp, vp, vp]),
     "pcnerf_nof_train_workspace_bytes": (c_size, [i64]),
     "pcnerf_set_train_math": (c_int, [c_int]),
-    "pcnerf_set_remat_version": (c_int, [c_int]),
     "pcnerf_set_composite_group": (c_int, [c_int]),
     "pcnerf_set_eval_math": (c_int, [c_int]),
     "pcnerf_set_query_geometry": (c_int, [c_int]),

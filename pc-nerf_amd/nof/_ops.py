@@ -122,23 +122,24 @@ TRAIN_MATH = {"fp32": 0, "f16x2_3": 1, "f16x2_4": 2, "f16x2_3_fused": 1}
 _TRAIN_FUSED = True   # the library's own default is mode 1 (f16x2_3)
 
 
+# The rematerialised backward has one layer kernel, k_bwd_remat3 ("version 4").  The pair below exists only because the
+# benchmark keys its kernel tags on get_remat_version(); nothing in the library is selected by it.
 def set_remat_version(version: int) -> int:
-    """Select the default training backward's layer kernel (pcnerf_set_remat_version): 4, k_bwd_remat3 with the
-    BatchNorm-backward epilogue on the W waves, the default; 2, k_bwd_remat2 (for A/B).  Returns the previous one.
-    Anything else (3, the retired D-wave-epilogue form, included) raises RuntimeError and changes nothing."""
-    prev = H.lib().pcnerf_set_remat_version(int(version))
-    if prev < 0:
-        raise RuntimeError(H.lib().pcnerf_last_error().decode())
-    return prev
+    """Accepts 4 (k_bwd_remat3, the only layer kernel of the rematerialised backward) and returns 4.  Anything else
+    raises RuntimeError: versions 2 (round 5's layer kernel) and 3 (the D-wave-epilogue form) are retired
+    (HISTORY.md)."""
+    if int(version) != 4:
+        raise RuntimeError(f"remat_version must be 4 (k_bwd_remat3), got {version!r}: versions 2 (round 5's layer "
+                           "kernel) and 3 (k_bwd_remat3 with the epilogue on the D waves) are retired and no longer "
+                           "built")
+    return 4
 
 
 def get_remat_version() -> int:
-    v = set_remat_version(4)
-    set_remat_version(v)
-    return v
+    return 4
 
 
-if os.environ.get("PCNERF_REMAT_VER"):   # (3, once an A/B switch, stops the import instead of being ignored)
+if os.environ.get("PCNERF_REMAT_VER"):   # (2 and 3, once A/B switches, stop the import instead of being ignored)
     set_remat_version(int(os.environ["PCNERF_REMAT_VER"]))
 
 

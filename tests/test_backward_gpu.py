@@ -67,20 +67,18 @@ def named(m):
     return dict(m.named_parameters())
 
 
-@pytest.fixture(params=["f16x2_3", "fp32", "f16x2_3_fused", "f16x2_3_fused_remat2", "f16x2_3_fused_store"])
+@pytest.fixture(params=["f16x2_3", "fp32", "f16x2_3_fused", "f16x2_3_fused_store"])
 def train_math(request):
     """The layered split math, fp32 MFMA, the default (fused forward + rematerialising backward, k_bwd_remat3 with
-    the BatchNorm-backward epilogue on the W waves: version 4), the same with round 5's layer kernel (k_bwd_remat2,
-    version 2), and the default forward with round 4's activation-store backward."""
+    the BatchNorm-backward epilogue on the W waves), and the default forward with round 4's activation-store
+    backward."""
     from nof import _ops
     mode = request.param
     prev = _ops.set_train_math("f16x2_3_fused" if mode.startswith("f16x2_3_fused") else mode)
     prevb = _ops.set_train_backward("store" if mode.endswith("_store") else "remat")
-    prevr = _ops.set_remat_version(2 if mode.endswith("_remat2") else 4)
     yield mode
     _ops.set_train_math(prev)
     _ops.set_train_backward(prevb)
-    _ops.set_remat_version(prevr)
 
 
 @pytest.mark.parametrize("name", ["pcnerf", "divide", "original"])
@@ -306,7 +304,7 @@ def test_train_grads_vs_oracle_large_chunks():
 
 def test_train_grads_vs_oracle_small_chunks(train_math):
     """Chunks of 1,000 samples (17-32 tiles, padded tails): most of the backward's workgroup pairs get no tile
-    (the layer kernels, k_g7 and k_wgrad_enc take a tile per pair and stride; FB_PAIRS = 128) and write zero partial
+    (the layer kernels and k_g7 take a tile per pair and stride; FB_PAIRS = 128) and write zero partial
     sets -- 96 rays x (16 + 32) samples = 2 coarse + 5 fine chunks.  BatchNorm over 1,000 samples makes these
     gradients sensitive to rounding: every train math, fp32 MFMA included, sits up to ~4e-4 from the float32 oracle
     while the oracle's thread-count spread is ~1e-5, so the reference here is the oracle's float64 evaluation

@@ -9,7 +9,7 @@ on top of it.
 3. the four functions against the reference's own outputs on jittered (off-ray) positions
    (tests/golden/inference_fns.npz), at test_parity_gpu's tolerances.
 4. loss.backward() through inference_train against the oracle's autograd (two thread counts + float64), the envelope
-   of test_backward_gpu.test_train_grads_vs_oracle_small_chunks, for the two rematerialising layer kernels.
+   of test_backward_gpu.test_train_grads_vs_oracle_small_chunks.
 5. refusals and the opt-in eval paths' fallback."""
 import numpy as np
 import pytest
@@ -298,15 +298,9 @@ def run_hip_grads(c, case):
     check_grads_elem(lambda k: named[k].grad.cpu().numpy(), list(named), c["grads"], "", case, noise=NOISE)
 
 
-@pytest.mark.parametrize("version", [4, 2])
-def test_inference_train_grads_small_chunks(version):
+def test_inference_train_grads_small_chunks():
     """(96, 48) jittered samples in chunks of 1,000 (5 chunks, the last 608)."""
-    c = cached_case(96, 48, 1000, 0, 31)
-    prev = _ops.set_remat_version(version)
-    try:
-        run_hip_grads(c, f"inference_train_chunk1000_remat{version}")
-    finally:
-        _ops.set_remat_version(prev)
+    run_hip_grads(cached_case(96, 48, 1000, 0, 31), "inference_train_chunk1000_remat4")
 
 
 def test_inference_train_grads_ragged_second_chunk():
