@@ -659,7 +659,8 @@ int pcnerf_se3_apply(const double* xi6, const double* poses12, int64_t n_poses, 
  * block_of_pose (n_poses) int32: the block of each pose; -1, and any index outside 0 .. n_blocks - 1, renders
  * nothing and is never used as an index.  For a pose with block b every output equals, bit for bit, what the
  * single-block entry gives for that pose with block b's folds and box.  A beam is clipped at the exit from its
- * block's box; nothing is composited across blocks.  Argument errors return -1 before anything is launched.
+ * block's box; nothing is composited across blocks unless asked: pcnerf_score_poses_through.  Argument errors return
+ * -1 before anything is launched.
  *
  * pcnerf_assign_blocks: block_of_pose[p] = the block whose box contains t_p (lo + margin <= t <= hi - margin on all
  *   three axes, float64) with the largest clearance min_m min(t_m - lo_m, hi_m - t_m), the lowest index on equal
@@ -691,6 +692,34 @@ int pcnerf_refine_poses_map(const float* points_sensor, int64_t n_beams, const d
                             float eps, double huber_delta, double min_sumw, double damping, double xi_tol, int iters,
                             void* workspace, size_t workspace_bytes, double* normal30, double* state,
                             double* poses12_out, double* eval_costs, uint8_t* accepted, void* stream);
+
+/* ---------------------------------------------------------------- scoring with beams carried through the blocks
+ * pcnerf_score_poses_through: pcnerf_score_poses_map with every beam carried on through the blocks it crosses.
+ *   Segment 0 is pcnerf_score_poses_map's render in block b_0 = block_of_pose[p], from near to the box exit.  With
+ *   te the float64 exit of the segment just rendered, block b' != b_k with the ray interval [tin, tout] in its box
+ *   (tout the entry's own exit expression before the clamp to near, tin its mirror image) is a candidate when
+ *   tin <= te + seam_tol, tout > te, neither is NaN and (float)tout > (float)max(te, tin); the next block is the
+ *   candidate with the largest tout, the lowest index on ties.  Segment k >= 1 is the same two-pass render of the
+ *   unchanged ray (o is still the sensor) with block b_k's folds from near_k = (float)max(te, tin) to the far that
+ *   pcnerf_score_poses_fold forms for box b_k at near = near_k; each segment has its own n_samples + n_importance
+ *   samples and its fine depth and sumw (dv_k, sv_k) are rounded once to float32.  The chain, float64, every operation
+ *   rounded separately, from T = 1, W = 0, N = 0: W += T sv_k; N += T (dv_k (sv_k + eps)); T = max(T (1 - sv_k), 0).
+ *   It ends after segment k when k + 1 == max_segments, T <= min_transmittance or no block is a candidate.  One
+ *   rendered segment: depth = dv_0, sumw = sv_0, pcnerf_score_poses_map's bits.  Otherwise depth = (float)(N / (W +
+ *   eps)) and sumw = (float)W: the compositing of the concatenated sample lists.  scores4 sums these two numbers
+ *   exactly as pcnerf_score_poses_map sums its own.  Space inside a gap of at most seam_tol is free; where boxes
+ *   overlap, the earlier block owns the beam up to its own exit.  n_segments_or_null / last_block_or_null
+ *   (n_poses, n_beams) int32: the segments rendered and the block of the last one; a pose without a block gets 0 and
+ *   -1 (and a zero scores4 row, NaN depth, zero sumw).  1 <= max_segments <= 16, seam_tol >= 0 (metres),
+ *   0 <= min_transmittance < 1.  `workspace` needs pcnerf_score_poses_workspace_bytes.  The per-beam outputs change
+ *   no bit of scores4.  Argument errors return -1 before anything is launched. */
+int pcnerf_score_poses_through(const float* points_sensor, int64_t n_beams, const double* poses12, int64_t n_poses,
+                               const int32_t* block_of_pose, int n_blocks, const double* boxes6, float near,
+                               int n_samples, int n_importance, const double* folds_coarse,
+                               const double* folds_fine, float eps, double huber_delta, double min_sumw,
+                               int max_segments, double seam_tol, double min_transmittance, void* workspace,
+                               size_t workspace_bytes, double* scores4, float* depth_or_null, float* sumw_or_null,
+                               int32_t* n_segments_or_null, int32_t* last_block_or_null, void* stream);
 
 /* ---------------------------------------------------------------- particle-filter update (Monte-Carlo localisation)
  * Weights, effective sample size and systematic resampling of a particle set on the device, in float64, with no

@@ -26,7 +26,10 @@
 //   gn_*               6. the per-beam Gauss-Newton pieces: the validity rule, the pose Jacobian
 //                         Jp = [J_o, o x J_o + d x J_d] of the left perturbation T' = exp(xi) T (delta o = rho + phi x o,
 //                         delta d = phi x d), the Huber weight and cost term.  Each kernel keeps its own accumulation;
-//   fr_block_of        which block of a map a pose of the two pose kernels is rendered against.
+//   fr_block_of        which block of a map a pose of the two pose kernels is rendered against;
+//   fr_pose_od, fr_box_interval, fr_segment_exit, fr_next_candidate, fr_chain_step
+//                      the walk of a beam over the blocks of a map and the compositing of its segments
+//                      (k_score_poses_through): nothing is composited across blocks unless asked.
 // Loops are bounded by S and I (the binary searches by their logarithm), never by data, and every LDS index is clamped,
 // so NaN rays (rng == 0, a non-finite point) cost time but cannot leave their slice.
 // Host side: the LDS slice size, the blocks per pose, the sample-count checks and the MAXB dispatch of the launchers.
@@ -186,6 +189,67 @@ __device__ __forceinline__ void fr_pose_ray(const double* pb, const float* __res
   }
   far = (float)far64;
   target = (float)rng;
+}
+
+// The pieces of a render carried through several blocks (k_score_poses_through, localize.hip): the float64 ray that
+// fr_pose_ray forms before its casts, the interval of a ray in a box, and one step of the chain over segments.
+// fr_pose_ray's operations one for one (the build does not contract), so the casts of o, d and rng are its row and
+// target, and fr_box_interval's tout is its box exit before the clamp to near.
+__device__ __forceinline__ void fr_pose_od(const double* T, const float* __restrict__ pt, double (&o)[3],
+                                           double (&d)[3], double& rng) {
+  const double px = (double)pt[0], py = (double)pt[1], pz = (double)pt[2];
+  rng = sqrt((px * px + py * py) + pz * pz);
+  const double ux = px / rng, uy = py / rng, uz = pz / rng;
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    d[m] = (T[3 * m] * ux + T[3 * m + 1] * uy) + T[3 * m + 2] * uz;
+    o[m] = T[9 + m];
+  }
+  const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+  for (int m = 0; m < 3; ++m) d[m] = d[m] / dn;
+}
+
+// [tin, tout] of the ray o + t d in box = [lo (3), hi (3)]: tout the minimum over the axes of max(t1, t2) (a NaN t2
+// counting as +inf), tin the mirror image, the maximum over the axes of min(t1, t2) (a NaN t1 counting as -inf); any
+// other NaN propagates
+__device__ __forceinline__ void fr_box_interval(const double (&o)[3], const double (&d)[3],
+                                                const double* __restrict__ box, double& tin, double& tout) {
+  const double nan64 = __builtin_nan("");
+  tin = 0.0;
+  tout = 0.0;
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    const double inv = 1.0 / d[m];
+    const double t1 = (box[m] - o[m]) * inv, t2 = (box[3 + m] - o[m]) * inv;
+    const double tm = t2 != t2 ? (double)INFINITY : (t1 != t1 ? nan64 : fmax(t1, t2));
+    const double tn = t1 != t1 ? -(double)INFINITY : (t2 != t2 ? nan64 : fmin(t1, t2));
+    tout = m == 0 ? tm : ((tout != tout || tm != tm) ? nan64 : fmin(tout, tm));
+    tin = m == 0 ? tn : ((tin != tin || tn != tn) ? nan64 : fmax(tin, tn));
+  }
+}
+
+// far of a segment that starts at near and leaves its box at tout: fr_pose_ray's clamp, in float64
+__device__ __forceinline__ double fr_segment_exit(double tout, float near) {
+  return tout != tout ? tout : fmax(tout, (double)near);
+}
+
+// Is the box with interval [tin, tout] a candidate for the segment after one that ended at te?  It must begin no later
+// than seam_tol past te, end after te, and be non-empty in float32, where the segment is rendered.
+__device__ __forceinline__ bool fr_next_candidate(double tin, double tout, double te, double seam_tol) {
+  return tin == tin && tout == tout && tin <= te + seam_tol && tout > te && (float)tout > (float)fmax(te, tin);
+}
+
+// One segment (depth dv, hit probability sv, each rounded to float32) joins the chain: T the transmittance in front of
+// it, W the hit probability so far, N the unnormalised depth sum.  1 - sum w = prod (1 - p) (render.py:51-61), so this
+// is the compositing of the concatenated sample lists.
+__device__ __forceinline__ void fr_chain_step(float dv, float sv, float eps, double& T, double& W, double& N) {
+  const double s = (double)sv, v = (double)dv;
+  const double c = T * s;
+  W = W + c;
+  N = N + T * (v * (s + (double)eps));
+  T = T * (1.0 - s);
+  if (T < 0.0) T = 0.0;
 }
 
 // value a of cat(zc, fs)

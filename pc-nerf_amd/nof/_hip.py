@@ -178,6 +178,9 @@ _SIGS = {
     "pcnerf_refine_poses_map": (c_int, [vp, i64, vp, i64, vp, c_int, vp, c_float, c_int, c_int, vp, vp, c_float,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
                                         vp, c_size, vp, vp, vp, vp, vp, vp]),
+    "pcnerf_score_poses_through": (c_int, [vp, i64, vp, i64, vp, c_int, vp, c_float, c_int, c_int, vp, vp, c_float,
+                                           ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
+                                           vp, c_size, vp, vp, vp, vp, vp, vp]),
     "pcnerf_mcl_weights_workspace_bytes": (c_size, [i64]),
     "pcnerf_mcl_weights": (c_int, [vp, vp, vp, i64, vp, ctypes.c_double, ctypes.c_double, vp, c_size, vp, vp, vp, vp,
                                    vp, vp]),

@@ -1112,3 +1112,71 @@ def map_op_names() -> list:
     """The operators of the map and particle-filter layer (tests)."""
     return ["assign_blocks", "score_poses_map", "pose_normal_eq_map", "refine_poses_map", "mcl_weights",
             "systematic_resample"]
+
+
+# ----------------------------------------------------------------------------------------------- through the blocks
+# score_poses_map with every beam carried on through the blocks it crosses (include/pcnerf_hip.h).  Reads no
+# process-wide selector.
+THROUGH_MAX_SEGMENTS = 16
+
+
+def check_through_params(op: str, max_segments: int, seam_tol: float, min_transmittance: float) -> None:
+    if not 1 <= max_segments <= THROUGH_MAX_SEGMENTS:
+        raise RuntimeError(f"pcnerf::{op}: max_segments = {max_segments}, must be 1 .. {THROUGH_MAX_SEGMENTS}")
+    if not seam_tol >= 0.0:
+        raise RuntimeError(f"pcnerf::{op}: seam_tol = {seam_tol}, must be >= 0")
+    if not 0.0 <= min_transmittance < 1.0:
+        raise RuntimeError(f"pcnerf::{op}: min_transmittance = {min_transmittance}, must be in [0, 1)")
+
+
+@torch.library.custom_op(f"{NS}::score_poses_through", mutates_args=())
+def score_poses_through(points: Tensor, poses12: Tensor, block_of_pose: Tensor, boxes6: Tensor, folds_coarse: Tensor,
+                        folds_fine: Tensor, near: float, n_samples: int, n_importance: int, eps: float,
+                        huber_delta: float, min_sumw: float, max_segments: int, seam_tol: float,
+                        min_transmittance: float,
+                        want_beams: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """score_poses_map with every beam carried through up to max_segments blocks, block_of_pose[p] first: (scores4,
+    depth, sumw (P, R) float32, n_segments, last_block (P, R) int32), the four per-beam tensors (0,) unless
+    want_beams.  A beam of one segment has score_poses_map's bits; a pose without a block gets a zero scores4 row, NaN
+    depth, zero sumw, n_segments 0 and last_block -1 (pcnerf_score_poses_through)."""
+    op = "score_poses_through"
+    _layout(op, "points", points, (None, 3))
+    _layout(op, "poses12", poses12, (None, 12), torch.float64)
+    _layout(op, "block_of_pose", block_of_pose, (poses12.shape[0],), torch.int32)
+    B = _check_map(op, boxes6, folds_coarse, folds_fine)
+    check_score_samples(op, n_samples, n_importance)
+    check_through_params(op, int(max_segments), float(seam_tol), float(min_transmittance))
+    _need_on_device(op, points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine)
+    R, Pn = points.shape[0], poses12.shape[0]
+    dev = points.device
+    scores = torch.empty((Pn, 4), dtype=torch.float64, device=dev)
+    shape = (Pn, R) if want_beams else (0,)
+    depth = torch.empty(shape, dtype=torch.float32, device=dev)
+    sumw = torch.empty(shape, dtype=torch.float32, device=dev)
+    nseg = torch.empty(shape, dtype=torch.int32, device=dev)
+    last = torch.empty(shape, dtype=torch.int32, device=dev)
+    nbytes = int(H.lib().pcnerf_score_poses_workspace_bytes(Pn, R))
+    ws = _ws(nbytes, dev)
+    H.check(H.lib().pcnerf_score_poses_through(
+        points.data_ptr(), R, poses12.data_ptr(), Pn, block_of_pose.data_ptr(), B, boxes6.data_ptr(), float(near),
+        int(n_samples), int(n_importance), folds_coarse.data_ptr(), folds_fine.data_ptr(), float(eps),
+        float(huber_delta), float(min_sumw), int(max_segments), float(seam_tol), float(min_transmittance),
+        ws.data_ptr(), nbytes, scores.data_ptr(), depth.data_ptr() if want_beams else None,
+        sumw.data_ptr() if want_beams else None, nseg.data_ptr() if want_beams else None,
+        last.data_ptr() if want_beams else None, H.stream_of(points)))
+    return scores, depth, sumw, nseg, last
+
+
+@score_poses_through.register_fake
+def _(points, poses12, block_of_pose, boxes6, folds_coarse, folds_fine, near, n_samples, n_importance, eps,
+      huber_delta, min_sumw, max_segments, seam_tol, min_transmittance, want_beams):
+    R, Pn = points.shape[0], poses12.shape[0]
+    shape = (Pn, R) if want_beams else (0,)
+    return (points.new_empty((Pn, 4), dtype=torch.float64), points.new_empty(shape, dtype=torch.float32),
+            points.new_empty(shape, dtype=torch.float32), points.new_empty(shape, dtype=torch.int32),
+            points.new_empty(shape, dtype=torch.int32))
+
+
+def through_op_names() -> list:
+    """The operator of the render carried through the blocks (tests)."""
+    return ["score_poses_through"]

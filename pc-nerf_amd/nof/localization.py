@@ -247,7 +247,8 @@ def localize_scan(model_coarse, model_fine, points_sensor: torch.Tensor, poses, 
 # ----------------------------------------------------------------------------------------------- maps of blocks
 # A PC-NeRF map is several parent blocks, each with its own pair of networks and its own AABB.  Every pose is rendered
 # against exactly one block -- its own -- and a beam is clipped where it leaves that block's box: nothing is composited
-# across blocks.  A block's AABB encloses the scans it was built from, so the sensor's own block sees the scene.
+# across blocks unless asked: ``score_poses_through`` (below) carries a beam on into the blocks it enters.  A block's
+# AABB encloses the scans it was built from, so the sensor's own block sees the scene.
 class BlockMap:
     """B >= 1 parent blocks on the device: ``folds_c`` / ``folds_f`` (B, 64) float64 (row b = pcnerf::fold_eval's
     output of block b's coarse / fine network) and ``boxes`` (B, 6) float64 rows [lo, hi].  Boxes may overlap."""
@@ -371,3 +372,71 @@ def localize_scan_map(block_map: BlockMap, points_sensor: torch.Tensor, poses, *
     r = refine_poses_map(block_map, pts, T.cpu()[idx], ids_host[idx], iters=int(refine_iters), **kw)
     best, refined = _winner_of_refined(r, order, same_basin_tol, mc, n_usable)
     return MapLocalizationResult(best[2].pose, float(best[0]), best[1], scores, refined, int(ids_host[best[1]]), ids)
+
+
+# ----------------------------------------------------------------------------------------------- through the blocks
+# The one exception to "every pose is rendered against one block": a beam that leaves its block's box goes on into the
+# block it enters, and the segments are composited (torch.ops.pcnerf.score_poses_through).  Scoring and scan synthesis
+# only: the refinement stays clipped, so localize_scan_map scores and refines under one model.
+class ThroughScores(NamedTuple):
+    cost: torch.Tensor            # (P,) float64: sum over the valid beams of rho(r)
+    n_valid: torch.Tensor         # (P,) int64
+    abs_residual: torch.Tensor    # (P,) float64: sum over the valid beams of |r|
+    hit: torch.Tensor             # (P,) float64: sum over the usable beams of sumw
+    depth: Optional[torch.Tensor]   # (P, R) float32 or None
+    sumw: Optional[torch.Tensor]    # (P, R) float32 or None
+    n_segments: Optional[torch.Tensor]   # (P, R) int32 or None: the segments rendered (0: the pose has no block)
+    last_block: Optional[torch.Tensor]   # (P, R) int32 or None: the block of the last segment (-1: none)
+
+
+class SynthesizedScan(NamedTuple):
+    points_sensor: torch.Tensor   # (R, 3) float32: unit direction x depth
+    depth: torch.Tensor           # (R,) float32
+    hit: torch.Tensor             # (R,) float32: the chain's sumw
+    n_segments: torch.Tensor      # (R,) int32
+    last_block: torch.Tensor      # (R,) int32
+
+
+def score_poses_through(block_map: BlockMap, points_sensor: torch.Tensor, poses, blocks=None, *,
+                        max_segments: int = 4, seam_tol: float = 1e-3, min_transmittance: float = 1e-3,
+                        N_samples: int = 64, N_importance: int = 128, huber_delta: float = 0.0, min_sumw: float = 0.5,
+                        near: float = 0.05, want_depth: bool = False) -> ThroughScores:
+    """score_poses_map with every beam carried through the blocks it crosses.  Segment 0 is score_poses_map's render in
+    the pose's own block; where the beam leaves that box, the block it enters within ``seam_tol`` metres (among several
+    the one it stays in longest) renders the next segment with its own networks and its own N_samples + N_importance
+    samples, and so on for at most ``max_segments`` segments or until the transmittance in front of the next segment
+    is at most ``min_transmittance``.  The segments are composited as one sample list; a beam that never leaves its
+    block keeps score_poses_map's bits.  ``want_depth`` also returns the (P, R) depth, sumw, segment count and last
+    block; it changes no bit of the scores."""
+    pts = _scan_points(points_sensor)
+    _torch_ops.check_score_samples("score_poses_through", int(N_samples), int(N_importance))
+    _torch_ops.check_through_params("score_poses_through", int(max_segments), float(seam_tol),
+                                    float(min_transmittance))
+    rows = _poses12(poses, pts.device)
+    ids = _block_ids(block_map, rows, blocks)
+    s4, depth, sumw, nseg, last = P.score_poses_through(
+        pts, rows, ids, block_map.boxes, block_map.folds_c, block_map.folds_f, float(near), int(N_samples),
+        int(N_importance), EPSILON, float(huber_delta), float(min_sumw), int(max_segments), float(seam_tol),
+        float(min_transmittance), bool(want_depth))
+    cost, n_valid, abs_r, hit = s4.t().contiguous()
+    beams = (depth, sumw, nseg, last) if want_depth else (None, None, None, None)
+    return ThroughScores(cost, n_valid.round().to(torch.int64), abs_r, hit, *beams)
+
+
+def synthesize_scan(block_map: BlockMap, directions_sensor: torch.Tensor, pose, blocks=None, *,
+                    max_segments: int = 4, seam_tol: float = 1e-3, min_transmittance: float = 1e-3,
+                    N_samples: int = 64, N_importance: int = 128, near: float = 0.05) -> SynthesizedScan:
+    """The scan the map predicts from ``pose`` (4, 4) along ``directions_sensor`` (R, 3, sensor frame, on the device,
+    any non-zero length): one call of ``torch.ops.pcnerf.score_poses_through`` whose scoring terms are not used.
+    ``blocks``: the pose's block (one integer in a sequence; None: ``assign_blocks``)."""
+    dirs = _scan_points(directions_sensor)
+    T = torch.as_tensor(pose, dtype=torch.float64).detach()
+    if tuple(T.shape) != (4, 4):
+        raise RuntimeError(f"synthesize_scan: pose must be (4, 4); got {tuple(T.shape)}")
+    s = score_poses_through(block_map, dirs, T[None], blocks, max_segments=max_segments, seam_tol=seam_tol,
+                            min_transmittance=min_transmittance, N_samples=N_samples, N_importance=N_importance,
+                            near=near, want_depth=True)
+    d = dirs.double()
+    unit = (d / torch.linalg.norm(d, dim=-1, keepdim=True)).float()
+    depth = s.depth[0]
+    return SynthesizedScan(unit * depth[:, None], depth, s.sumw[0], s.n_segments[0], s.last_block[0])

@@ -3,7 +3,9 @@ device and whose step is a handful of enqueued launches with no host synchronisa
 
 ``ParticleFilter.step`` is predict (every particle moves by the odometry twist plus Gaussian noise drawn on the
 device, ``apply_twists``' kernel, then ``torch.ops.pcnerf.assign_blocks``), update (``torch.ops.pcnerf.score_poses_map``
-renders the scan under every particle against the particle's own block; ``torch.ops.pcnerf.mcl_weights`` turns the
+renders the scan under every particle against the particle's own block -- or, with ``through=True``,
+``torch.ops.pcnerf.score_poses_through`` carries its beams on through the blocks they cross;
+``torch.ops.pcnerf.mcl_weights`` turns the
 sums into normalised float64 weights, their effective sample size and the best particle) and resample
 (``torch.ops.pcnerf.systematic_resample``: the decision ``ess >= ess_frac * P`` is taken on the device from the
 weights' own output buffer, and the particles, their blocks and their log-weights are gathered there).  Nothing is read
@@ -53,15 +55,23 @@ def _six(v, name: str, scalar_ok: bool = False):
 class ParticleFilter:
     """P particles (poses, sensor -> world) over a ``BlockMap``.  ``poses`` (P, 4, 4) float64, host or device;
     the render settings are score_poses' (N_samples, N_importance, huber_delta, min_sumw, near); ``miss_cost``
-    defaults to the map's ``default_miss_cost``; ``beta`` scales the mean cost into a log-likelihood.
+    defaults to the map's ``default_miss_cost``; ``beta`` scales the mean cost into a log-likelihood.  ``through``:
+    the update carries every beam through the blocks it crosses (``nof.localization.score_poses_through`` with
+    ``max_segments``, ``seam_tol`` and ``min_transmittance``) instead of clipping it at the particle's own block.
 
     State (device): ``poses12`` (P, 12) float64 rows [R row-major, t], ``blocks`` (P,) int32, ``logw`` and ``w`` (P,)
     float64 (normalised), ``ess`` (1,) float64, ``best`` and ``degenerate`` (1,) int32, ``scores4`` (P, 4)."""
 
     def __init__(self, block_map: BlockMap, poses, *, beta: float = 1.0, miss_cost: Optional[float] = None,
                  margin: float = 0.0, N_samples: int = 64, N_importance: int = 128, huber_delta: float = 0.0,
-                 min_sumw: float = 0.5, near: float = 0.05):
+                 min_sumw: float = 0.5, near: float = 0.05, through: bool = False, max_segments: int = 4,
+                 seam_tol: float = 1e-3, min_transmittance: float = 1e-3):
         _torch_ops.check_score_samples("ParticleFilter", int(N_samples), int(N_importance))
+        _torch_ops.check_through_params("ParticleFilter", int(max_segments), float(seam_tol),
+                                        float(min_transmittance))
+        self.through = bool(through)
+        self.chain = dict(max_segments=int(max_segments), seam_tol=float(seam_tol),
+                          min_transmittance=float(min_transmittance))
         self.map = block_map
         dev = block_map.device
         self.poses12 = _poses12(poses, dev)
@@ -122,9 +132,16 @@ class ParticleFilter:
             raise RuntimeError(f"points_sensor must be (R, 3); got {tuple(points_sensor.shape)}")
         pts = points_sensor.detach().float().contiguous()
         r = self.render
-        self.scores4, _, _ = P.score_poses_map(pts, self.poses12, self.blocks, self.map.boxes, self.map.folds_c,
-                                               self.map.folds_f, r["near"], r["N_samples"], r["N_importance"],
-                                               EPSILON, r["huber_delta"], r["min_sumw"], False)
+        if self.through:
+            c = self.chain
+            self.scores4 = P.score_poses_through(pts, self.poses12, self.blocks, self.map.boxes, self.map.folds_c,
+                                                 self.map.folds_f, r["near"], r["N_samples"], r["N_importance"],
+                                                 EPSILON, r["huber_delta"], r["min_sumw"], c["max_segments"],
+                                                 c["seam_tol"], c["min_transmittance"], False)[0]
+        else:
+            self.scores4, _, _ = P.score_poses_map(pts, self.poses12, self.blocks, self.map.boxes, self.map.folds_c,
+                                                   self.map.folds_f, r["near"], r["N_samples"], r["N_importance"],
+                                                   EPSILON, r["huber_delta"], r["min_sumw"], False)
         rng = torch.linalg.norm(points_sensor.detach().double(), dim=-1).float()   # localize_scan's count, on the device
         n_usable = (torch.isfinite(rng) & (rng > 0)).sum().to(torch.float64).reshape(1)
         self.w, self.logw, self.ess, self.best, self.degenerate = P.mcl_weights(
